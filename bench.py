@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
-"""bench.py -- EKF predict+update steps/sec at batch N on MI355X, with roofline and CPU baseline.
+"""bench.py -- EKF predict+update steps/sec at batch N on MI355X, with roofline (CPU baseline and other configs with --full).
 
 Contract (driver):  python bench.py --gpus N --steps K --warmup W   -> ONE JSON line on rank 0.
+A plain run measures the headline workload only: set up, warm up, time exactly K steps, print the line (`ms_per_step` = milliseconds
+per timed step).  `--full` adds everything else, as its own runs after the headline: the cold-launch sample, the CPU baseline of the
+oracle and the other configurations under "extra" (`--no-cpu-baseline` / `--no-extras` trim a `--full` run).  `--dump-outputs DIR`
+writes what the last timed step handed its caller (x, P, the residual y) as DIR/<name>.npy; the inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
 For N > 1 the driver launches one rank per GPU with torch.distributed.run (RCCL); the batch axis shards with no
 data-path collective (filters are independent).  Default scaling is weak: every rank owns `--batch` filters;
 `--global-batch G` fixes the total instead (strong scaling, rank r owns rednose_amd.helpers.sharding.shard_range(G, r, N)).
@@ -275,9 +280,11 @@ def gen_dir(names):
   return ensure_generated(names, **({'folder': os.environ['RN_GEN_DIR']} if 'RN_GEN_DIR' in os.environ else {}))
 
 
-def run_model(torch, dist, model, n, K, W, dev, rank, world, only_kind=None):
+def run_model(torch, dist, model, n, K, W, dev, rank, world, only_kind=None, cold=True):
   """Warm up W steps, time exactly K steps (barrier + synchronize on both sides).  Returns a timing dict; `wall` and `dev_ms`
-  are this rank's (the aggregation over ranks is the caller's: sharding.aggregate_throughput)."""
+  are this rank's (the aggregation over ranks is the caller's: sharding.aggregate_throughput).  `outputs` holds what the last timed
+  step handed its caller: the filtered state and covariance and the residual written over that step's observation.  `cold` takes
+  the cold-launch sample first (`cold_launch_us`, None without it)."""
   from rednose_amd.helpers.ekf_sym import BatchedEKF
   M = model_class(model)
   if rank == 0:
@@ -351,13 +358,15 @@ def run_model(torch, dist, model, n, K, W, dev, rank, world, only_kind=None):
   # The COLD figure, reported next to the steady one (top-level "cold_launch_us"): the mean of the first COLD_LAUNCHES launches after the
   # device has idled >= 100 ms -- what a caller that steps a batch once in a while sees (empty queue, clocks down): host -> doorbell ->
   # command processor -> dispatch is exposed until the host is ahead (profiles/r4_short_run_per_launch.txt: 35.8 / 19.7 / 18.4 us, then flat).
-  torch.cuda.synchronize()
-  time.sleep(0.12)
-  a_, b_ = untimed_group(0, COLD_LAUNCHES)
-  torch.cuda.synchronize()
-  cold_us = a_.elapsed_time(b_) * 1e3 / COLD_LAUNCHES
-  f.x.copy_(x_keep)
-  f.P.copy_(P_keep)
+  cold_us = None
+  if cold:
+    torch.cuda.synchronize()
+    time.sleep(0.12)
+    a_, b_ = untimed_group(0, COLD_LAUNCHES)
+    torch.cuda.synchronize()
+    cold_us = a_.elapsed_time(b_) * 1e3 / COLD_LAUNCHES
+    f.x.copy_(x_keep)
+    f.P.copy_(P_keep)
   if os.environ.get("RN_BENCH_NO_STEADY") != "1":
     t_warm = time.perf_counter()
     prev = None
@@ -408,6 +417,7 @@ def run_model(torch, dist, model, n, K, W, dev, rank, world, only_kind=None):
   bytes_per_step = 8.0 * (2 * (D + E * E) + 2 * float(np.mean(zdims)))
   return dict(M=M, D=D, E=E, Z=float(np.mean(zdims)), wall=wall, dev_ms=dev_ms, bytes_per_step=bytes_per_step, gen=gen,
               kinds=sorted(set(s[0] for s in sched[W:W + K])), steady=steady, cold_launch_us=cold_us,
+              outputs={"x": f.x, "P": f.P, "y": sched[W + K - 1][2]} if K > 0 else None,
               launch_us_median=float(np.median(groups)) if groups else None, launch_us_groups=len(groups),
               group_us=[round(g_, 3) for g_ in groups] if os.environ.get("RN_BENCH_MARK_EVERY") else None)
 
@@ -701,6 +711,31 @@ def msckf_extra(torch, dev):
           "note": "fused predict + feature-track update (Z = 6 projected to 3), one filter per wavefront, per-filter landmarks"}
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6    # --dump-outputs: at most this much in all (64 MB); larger outputs are written as a seeded sample of filters
+
+
+def dump_outputs(outputs, out_dir):
+  """Write the arrays of `outputs` (torch tensors with the filter on axis 0) as out_dir/<name>.npy in float64.  When they exceed
+  DUMP_LIMIT_BYTES together, the same fixed, seeded sample of filters (sorted indices) is taken from every array.  Returns a summary
+  for the result line."""
+  n = int(next(iter(outputs.values())).shape[0])
+  per_filter = sum(int(np.prod(v.shape[1:])) * 8 for v in outputs.values())
+  keep = min(n, DUMP_LIMIT_BYTES // max(1, per_filter))
+  idx = None
+  if keep < n:
+    import torch
+    idx = torch.as_tensor(np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False)))
+  os.makedirs(out_dir, exist_ok=True)
+  files = {}
+  for name, v in outputs.items():
+    a = v if idx is None else v.index_select(0, idx.to(v.device))
+    a = a.detach().cpu().numpy().astype(np.float64, copy=False)
+    np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    files[name] = list(a.shape)
+  return {"dir": os.path.abspath(out_dir), "files": files, "filters": keep, "of_filters": n,
+          "sample": None if idx is None else f"{keep} filters drawn with numpy default_rng(0), sorted"}
+
+
 def _free_port():
   import socket
   s = socket.socket()
@@ -790,8 +825,12 @@ def main():
   ap.add_argument("--batch", type=int, default=None, help="filters per GPU (default 65536; 16384 for --model live): weak scaling")
   ap.add_argument("--global-batch", type=int, default=None, help="total filters over all GPUs (strong scaling): rank r owns shard_range(G, r, N)")
   ap.add_argument("--model", default="kinematic6", choices=["kinematic6", "kinematic", "kinematic9", "live"])
-  ap.add_argument("--no-cpu-baseline", action="store_true")
-  ap.add_argument("--no-extras", action="store_true", help="skip the additional configs reported under 'extra'")
+  ap.add_argument("--full", action="store_true",
+                  help="also measure what the headline figure does not need: cold-launch sample, CPU baseline, the configs under 'extra'")
+  ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+  ap.add_argument("--no-extras", action="store_true", help="with --full: skip the additional configs reported under 'extra'")
+  ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                  help="write what the last timed step computed (x, P, residual y; rank 0's filters) as DIR/<name>.npy, float64, <= 64 MB")
   ap.add_argument("--sweep", default=None, metavar="1,2,4,8",
                   help="run every listed GPU count in this one invocation (weak: --batch per GPU; strong: --global-batch or "
                        "batch x the largest count) and print ONE JSON line holding all points; counts this node cannot run are marked 'not run'")
@@ -840,14 +879,18 @@ def main():
     n, scaling = hi - lo, "strong"
   else:
     n, scaling = args.batch or (16384 if args.model == "live" else 65536), "weak"
-  r = run_model(torch, dist if use_dist else None, args.model, n, K, W, dev, rank, world)
+  r = run_model(torch, dist if use_dist else None, args.model, n, K, W, dev, rank, world, cold=args.full)
   M, D, E = r["M"], r["D"], r["E"]
+  dumped = None
+  if args.dump_outputs and rank == 0 and r["outputs"] is not None:
+    dumped = dump_outputs(r["outputs"], args.dump_outputs)
+  r.pop("outputs")
   agg_dev = dev if (use_dist and os.environ.get("RN_BENCH_BACKEND", "nccl") == "nccl") else None
   value, steps_total, wall_max = sharding.aggregate_throughput(n * K, r["wall"], dist if use_dist else None, device=agg_dev)
   _, _, dev_ms_max = sharding.aggregate_throughput(1.0, r["dev_ms"], dist if use_dist else None, device=agg_dev)
 
   extra = {}
-  if not args.no_extras and world == 1 and args.model == "kinematic6":
+  if args.full and not args.no_extras and world == 1 and args.model == "kinematic6":
     def stepwise(om, on, oK, oW, kernel, key=None, only_kind=None, note=None):
       o = run_model(torch, None, om, on, oK, oW, dev, rank, world, only_kind=only_kind)
       ls = o["dev_ms"] * 1e-3 / oK
@@ -882,11 +925,11 @@ def main():
       "n_gpus": dist.get_world_size() if use_dist else 1,        # the ranks that actually ran (the process group's own count)
       "steps": K,
       "warmup": W,
-      # launches of the same entry point that ran BEFORE the W warm-up steps and are part of neither W nor K (the cold sample and the
-      # steady-state groups: steady_state_warmup below), and the mean duration of a launch on the idle device -- top-level, so that a
-      # reader of the line sees what "warmup" does not say
-      "untimed_launches": int(r["steady"]["launches"]) + COLD_LAUNCHES,
-      "cold_launch_us": round(r["cold_launch_us"], 3),
+      # launches of the same entry point that ran BEFORE the W warm-up steps and are part of neither W nor K (the cold sample of --full
+      # and the steady-state groups: steady_state_warmup below), and the mean duration of a launch on the idle device (--full only) --
+      # top-level, so that a reader of the line sees what "warmup" does not say
+      "untimed_launches": int(r["steady"]["launches"]) + (COLD_LAUNCHES if r["cold_launch_us"] is not None else 0),
+      "cold_launch_us": round(r["cold_launch_us"], 3) if r["cold_launch_us"] is not None else None,
       "ms_per_step": wall_max * 1e3 / K,
       "higher_is_better": True,
       "scaling": scaling,
@@ -906,7 +949,7 @@ def main():
       out["roofline"]["group_us"] = r["group_us"]
     if force_dist:
       out["forced_process_group"] = {"backend": dist.get_backend(), "world_size": dist.get_world_size()}
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
       kind = 1 if args.model != "live" else 10
       cb, ncpu, flav, ckind = cpu_baseline(M.name, kind, M, n)
       one = cb["1core"]
@@ -925,6 +968,8 @@ def main():
       out["extra"] = extra
     if TRAFFIC_CARRIED:
       out["traffic_carried"] = dict(TRAFFIC_CARRIED)
+    if dumped:
+      out["dump_outputs"] = dumped
     print(json.dumps(out))
   if use_dist:
     dist.destroy_process_group()

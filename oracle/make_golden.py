@@ -615,6 +615,27 @@ def multi_obs_goldens():
         "; part B", NF, "x", TF, "calls,", int(nB.sum()) * NF, "observations")
 
 
+def ref_functions():
+  """The reference flavour's generated functions (f, F, H_mod, err, inv_err, h / H per kind, He) at the seeded inputs of
+  tests/test_oracle.py::ref_function_cases, for tests/test_oracle.py::test_port_flavour_equals_ref_flavour."""
+  for m in [m for m in sys.modules if m == "examples" or m.startswith("examples.")]:      # the inputs use this project's models
+    del sys.modules[m]
+  sys.path[:0] = [REPO, os.path.join(REPO, "tests")]
+  from test_oracle import REF_FUNCTION_MODELS, ref_function_cases
+  from oracle_lib import OracleLib
+  out = {}
+  for name in REF_FUNCTION_MODELS:
+    a = OracleLib(name, "ref")
+    kinds, cases = ref_function_cases(name, a)
+    out[f"{name}/dims"] = np.array([a.D, a.E, a.M])
+    out[f"{name}/zdims"] = np.array([a.zdim(k) for k in kinds])
+    for label, sym, args, size in cases:
+      o = np.zeros(size)
+      a.call(sym, *args, o)
+      out[f"{name}/{label}"] = o
+  np.savez_compressed(os.path.join(GOLD, "ref_functions.npz"), **out)
+  print("reference-flavour functions:", len(out), "arrays")
+
 if __name__ == "__main__":
   os.makedirs(GOLD, exist_ok=True)
   if len(sys.argv) > 1:          # python oracle/make_golden.py <function> ...: regenerate only those fixtures
@@ -634,5 +655,6 @@ if __name__ == "__main__":
   feature_goldens(T=15, cls_name="WideFeatureKalman", out_name="feature36_stream.npz", n_upd=6)
   perfilter_timelines()
   multi_obs_goldens()
+  ref_functions()
   for fn in sorted(os.listdir(GOLD)):
     print(fn, os.path.getsize(os.path.join(GOLD, fn)))

@@ -10,7 +10,7 @@ mkdir -p "$d"
 tail -5 "$d/pytest.log"
 ( time timeout 420 profiles/collect.sh "$tag" ) > "$d/collect.log" 2>&1
 tail -3 "$d/collect.log"
-( time timeout 240 python bench.py ) > "$d/bench.json" 2> "$d/bench.err"
+( time timeout 240 python bench.py --full ) > "$d/bench.json" 2> "$d/bench.err"
 tail -c 600 "$d/bench.err"
 # the driver-style short run (what `--steps 20 --warmup 5` reports: frac from the HIP events, frac_wall from the host's clock)
 ( time timeout 120 python bench.py --steps 20 --warmup 5 --no-extras ) > "$d/bench_short.json" 2> "$d/bench_short.err"

@@ -4,7 +4,8 @@ Pins, strongest first:
   * the four literals of /root/reference/examples/test_kinematic_kf.py:52-55 (7 decimal places there);
   * tests/golden/*.npz -- trajectories / single steps produced by the reference's own Python path
     (oracle/make_golden.py: EKF_sym._predict_python/_update_python over reference-generated C);
-  * oracle flavour `port` (our sympy front end) == flavour `ref` (reference gen_code) when both exist.
+  * oracle flavour `port` (our sympy front end) == flavour `ref` (reference gen_code): its recorded outputs
+    (tests/golden/ref_functions.npz) everywhere, the flavour itself where both exist.
 """
 import os
 
@@ -172,40 +173,56 @@ def test_thresholds_match_reference_table():
   assert abs(chi2_ppf(0.95, 6) - 12.591587243743978) < 1e-13
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="oracle/_ref not built (needs /root/reference)")
-@pytest.mark.parametrize("name", ["kinematic", "live", "kinematic6", "kinematic9", "feature", "rand5", "rand17"])
-def test_port_flavour_equals_ref_flavour(name):
-  """Our model front end (examples/ + rednose_amd.codegen.spec) must generate the same functions as the reference."""
-  a, b = OracleLib(name, "ref"), OracleLib(name, "port")
-  assert (a.D, a.E, a.M) == (b.D, b.E, b.M)
+REF_FUNCTION_MODELS = ["kinematic", "live", "kinematic6", "kinematic9", "feature", "rand5", "rand17"]
+
+
+def ref_function_cases(name, lib):
+  """The inputs at which the two flavours are compared, drawn from a seeded generator: (label, symbol, arguments, output size)
+  in call order.  oracle/make_golden.py (ref_functions) records the reference flavour's outputs at exactly these inputs."""
   rng = np.random.default_rng(3)
   if name == "live":
     from examples.live_kf import LiveKalman
     x = LiveKalman.initial_x + rng.normal(size=23) * np.array([100] * 3 + [0.2] * 4 + [3] * 3 + [0.1] * 3 + [0.01] * 3 + [0.01] + [0.5] * 3 + [0.02] * 3)
     kinds = [3, 4, 9, 10, 12, 13, 14, 19]
   else:
-    x = rng.normal(size=a.D)
+    x = rng.normal(size=lib.D)
     kinds = {"kinematic9": [1, 2, 3], "feature": [1, 2], "rand5": [1, 2, 3], "rand17": [1, 2, 3]}.get(name, [1])
   dt = 0.037
-  def both(sym, *args, shape):
-    oa, ob = np.zeros(shape), np.zeros(shape)
-    a.call(sym, *args, oa); b.call(sym, *args, ob)
-    assert_close(ob, oa, rtol=1e-13, floor=1e-15, what=f"{name}.{sym}")
-  both("f_fun", x, dt, shape=a.D)
-  both("F_fun", x, dt, shape=a.E * a.E)
-  both("H_mod_fun", x, shape=a.D * a.E)
-  dx = rng.normal(size=a.E) * 0.01
-  both("err_fun", x, dx, shape=a.D)
-  x2 = x + rng.normal(size=a.D) * 1e-3
-  both("inv_err_fun", x, x2, shape=a.E)
+  cases = [("f_fun", "f_fun", (x, dt), lib.D), ("F_fun", "F_fun", (x, dt), lib.E * lib.E), ("H_mod_fun", "H_mod_fun", (x,), lib.D * lib.E)]
+  dx = rng.normal(size=lib.E) * 0.01
+  cases.append(("err_fun", "err_fun", (x, dx), lib.D))
+  x2 = x + rng.normal(size=lib.D) * 1e-3
+  cases.append(("inv_err_fun", "inv_err_fun", (x, x2), lib.E))
   ea = np.array([0.3, -0.2, 7.0])       # landmark of the feature kind; ignored by kinds without extra args
   for k in kinds:
-    Z = a.zdim(k)
-    assert b.zdim(k) == Z
-    both(f"h_{k}", x, ea, shape=Z)
-    both(f"H_{k}", x, ea, shape=Z * a.D)
+    Z = lib.zdim(k)
+    cases += [(f"h_{k}", f"h_{k}", (x, ea), Z), (f"H_{k}", f"H_{k}", (x, ea), Z * lib.D)]
     if name == "feature" and k == 2:
-      both("He_2", x, ea, shape=Z * 3)
+      cases.append(("He_2", "He_2", (x, ea), Z * 3))
+  return kinds, cases
+
+
+@pytest.mark.parametrize("name", REF_FUNCTION_MODELS)
+def test_port_flavour_equals_ref_flavour(name):
+  """Our model front end (examples/ + rednose_amd.codegen.spec) must generate the same functions as the reference: the port flavour
+  against the reference flavour's outputs recorded in tests/golden/ref_functions.npz, and against the reference flavour itself
+  wherever oracle/_ref can be built."""
+  b = OracleLib(name, "port")
+  g = golden("ref_functions.npz")
+  a = OracleLib(name, "ref") if HAVE_REF else None
+  assert tuple(int(v) for v in g[f"{name}/dims"]) == (b.D, b.E, b.M)
+  if a is not None:
+    assert (a.D, a.E, a.M) == (b.D, b.E, b.M)
+  kinds, cases = ref_function_cases(name, b)
+  assert [b.zdim(k) for k in kinds] == [int(v) for v in g[f"{name}/zdims"]]
+  for label, sym, args, size in cases:
+    ob = np.zeros(size)
+    b.call(sym, *args, ob)
+    assert_close(ob, g[f"{name}/{label}"], rtol=1e-13, floor=1e-15, what=f"{name}.{sym} (recorded reference flavour)")
+    if a is not None:
+      oa = np.zeros(size)
+      a.call(sym, *args, oa)
+      assert_close(ob, oa, rtol=1e-13, floor=1e-15, what=f"{name}.{sym}")
 
 
 def test_zero_dt_shortcut_is_guarded_symbolically():
