@@ -225,7 +225,43 @@ extern "C" {
    * too old for their ring (bits 4 | 5) on the stream, without moving the flag bytes through the host */          \
   int RN_FN(name, batch_flags_set)(uint8_t *flags, const uint8_t *mask, int value, int64_t n, void *stream);
 
-#define RN_DECLARE_BATCH_KIND_MASKED(name, k)                                                                    \
+/* Per-filter timelines with the in-order bookkeeping ON THE DEVICE: the filters' times ft (n doubles, NaN = not started) and their
+ * rings stay in device memory, and a call in which no filter is late costs the host one integer.  All pointers are DEVICE pointers, both
+ * calls are asynchronous on `stream`, status codes as in section 2.
+ *
+ * batch_timeline_plan is PURE -- it writes only its outputs, never ft or a ring.  Per filter i, with active == NULL meaning all:
+ *   inactive                               dt_out = 0,                          act_out = 0, late_out = 0
+ *   active, ft NaN or t >= ft              dt_out = isnan(ft) ? 0 : t - ft,     act_out = 1, late_out = 0
+ *   active, t < ft  (late)                 dt_out = 0,                          act_out = 0, late_out = 1, counted in *n_late
+ * dt_out / act_out are the dt_vec / active of the `_masked` entry points below.  *n_late (one int32) ACCUMULATES, one vector atomic per
+ * wavefront with a late filter: zero it before the call or compare with its value before.  It may be pinned host memory mapped
+ * into the device (hipHostMallocMapped: readable after one wait for the stream), or device memory followed by a 4-byte copy.
+ * z_keep (may be NULL): z_count doubles of z_src copied aside, for the checkpoint -- the step overwrites z with the residuals.
+ *
+ * batch_timeline_push is the whole checkpoint of a call (EKFSym::checkpoint, ekf_sym.cc:142-156, for n instances) in ONE launch, to
+ * be enqueued behind the step.  For every filter with act[i] != 0: ft[i] = t[i]; its ring advances --
+ *   full = length >= K;  head = full ? (head + 1) % K : head;  length = full ? length : length + 1;  slot = (head + length - 1) % K
+ * -- and entry `slot` takes t[i], x[i] (D), P[i] (E * E), kind, nobs and the call's nobs observations AS THEY CAME: observation j of
+ * filter i is read at z_obs + i * z_stride_f + j * z_stride_o (Z of the kind; strides in doubles), its noise at R + i * r_stride_f +
+ * j * r_stride_o (Z * Z; r_per_filter == 0: shared by the filters, r_stride_f ignored), its extra arguments (kinds that take them)
+ * at ea + i * ea_stride_f + j * ea_stride_o.  Ring layout, K entries per filter: ring_t (K, n), ring_x (K, n, D), ring_P (K, n, E, E),
+ * ring_kind / ring_nobs (K, n) int32, ring_z (K, n, nmax, zmax), ring_R (K, n, nmax, zmax, zmax), ring_ea (K, n, nmax, eamax) with
+ * zmax = {name}_zmax() and eamax = max(1, largest {name}_kind_eadim); ring_head / ring_length (n) int64.  Only the Z / Z x Z / EA
+ * leading entries of an observation's slots are written.  1 <= nobs <= nmax.  K == 0 (ring pointers NULL): only ft is written. */
+#define RN_DECLARE_BATCH_TIMELINE(name)                                                                          \
+  int RN_FN(name, batch_timeline_plan)(const double *t, const uint8_t *active, const double *ft, int64_t n,       \
+                                       double *dt_out, uint8_t *act_out, uint8_t *late_out, int32_t *n_late,      \
+                                       const double *z_src, double *z_keep, int64_t z_count, void *stream);       \
+  int RN_FN(name, batch_timeline_push)(const double *t, const uint8_t *act, double *ft, const double *x,          \
+                                       const double *P, int64_t n, int64_t K, int64_t nmax, double *ring_t,       \
+                                       double *ring_x, double *ring_P, int32_t *ring_kind, int32_t *ring_nobs,    \
+                                       double *ring_z, double *ring_R, double *ring_ea, int64_t *ring_head,       \
+                                       int64_t *ring_length, int kind, int nobs, const double *z_obs,             \
+                                       int64_t z_stride_f, int64_t z_stride_o, const double *R, int r_per_filter, \
+                                       int64_t r_stride_f, int64_t r_stride_o, const double *ea,                  \
+                                       int64_t ea_stride_f, int64_t ea_stride_o, void *stream);
+
+#define RN_DECLARE_BATCH_KIND_MASKED(name, k)                                                                   \
   int RN_FN(name, batch_update_##k##_masked)(double *x, double *P, double *z, const double *R, int r_per_filter,  \
                                              const double *ea, int64_t n, int norm_quats, uint8_t *flags,         \
                                              const uint8_t *active, void *stream);                                \

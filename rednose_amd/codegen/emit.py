@@ -373,6 +373,49 @@ int {name}_batch_predict_update_{k.kind}{sfx}(double *x, double *P, const double
 }}""")
   hdr.append(f"int {name}_batch_flags_set(uint8_t *flags, const uint8_t *mask, int value, int64_t n, void *stream);")
 
+  # per-filter timelines with the in-order bookkeeping on the device (rn::k_timeline_plan / k_timeline_push, include/rednose_amd_filter.h):
+  # what every filter does in this call before the step, the call's checkpoint behind it
+  tl_plan = ("const double *t, const uint8_t *active, const double *ft, int64_t n, double *dt_out, uint8_t *act_out, uint8_t *late_out, "
+             "int32_t *n_late, const double *z_src, double *z_keep, int64_t z_count, void *stream")
+  abi.append(f"""int {name}_batch_timeline_plan({tl_plan}) {{
+  RN_REQUIRE(n >= 0 && t && ft && dt_out && act_out && late_out && n_late, rn::ERR_ARG);
+  RN_REQUIRE(z_count >= 0 && (z_keep == nullptr || z_count == 0 || (z_src != nullptr && z_src != z_keep)), rn::ERR_ARG);
+  if (n == 0) return rn::OK;
+  hipLaunchKernelGGL(rn::k_timeline_plan, dim3((unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024)), dim3(256), 0, (hipStream_t)stream,
+                     t, active, ft, n, dt_out, act_out, late_out, n_late, z_src, z_count > 0 ? z_keep : nullptr, z_count);
+  RN_HIP(hipGetLastError());
+  return rn::OK;
+}}""")
+  hdr.append(f"int {name}_batch_timeline_plan({tl_plan});")
+  tl_push = ("const double *t, const uint8_t *act, double *ft, const double *x, const double *P, int64_t n, int64_t K, int64_t nmax, "
+             "double *ring_t, double *ring_x, double *ring_P, int32_t *ring_kind, int32_t *ring_nobs, double *ring_z, double *ring_R, double *ring_ea, "
+             "int64_t *ring_head, int64_t *ring_length, int kind, int nobs, const double *z_obs, int64_t z_stride_f, int64_t z_stride_o, "
+             "const double *R, int r_per_filter, int64_t r_stride_f, int64_t r_stride_o, const double *ea, int64_t ea_stride_f, int64_t ea_stride_o, "
+             "void *stream")
+  eamax = max([ea_len(k) for k in spec.kinds] + [1])
+  tl_ea = " ".join(f"case {k.kind}: EA = {ea_len(k)}; break;" for k in spec.kinds)
+  abi.append(f"""int {name}_batch_timeline_push({tl_push}) {{
+  RN_REQUIRE(n >= 0 && K >= 0 && t && act && ft, rn::ERR_ARG);
+  const int Z = {name}_kind_zdim(kind);
+  int EA = -1;
+  switch (kind) {{ {tl_ea} default: break; }}
+  rn::TimelineRing r{{}};
+  rn::TimelineObs o{{}};
+  if (K > 0) {{
+    RN_REQUIRE(Z > 0 && EA >= 0 && nmax >= 1 && nobs >= 1 && nobs <= nmax, rn::ERR_ARG);
+    RN_REQUIRE(x && P && ring_t && ring_x && ring_P && ring_kind && ring_nobs && ring_z && ring_R && ring_ea && ring_head && ring_length, rn::ERR_ARG);
+    RN_REQUIRE(z_obs && R && (EA == 0 || ea) && z_stride_f >= 0 && z_stride_o >= 0 && r_stride_f >= 0 && r_stride_o >= 0 && ea_stride_f >= 0 && ea_stride_o >= 0, rn::ERR_ARG);
+    r = rn::TimelineRing{{K, nmax, ring_t, ring_x, ring_P, ring_kind, ring_nobs, ring_z, ring_R, ring_ea, ring_head, ring_length}};
+    o = rn::TimelineObs{{z_obs, R, ea, z_stride_f, z_stride_o, r_per_filter ? r_stride_f : 0, r_stride_o, ea_stride_f, ea_stride_o}};
+  }}
+  if (n == 0) return rn::OK;
+  hipLaunchKernelGGL(rn::k_timeline_push, dim3((unsigned)((n + 3) / 4 < 16384 ? (n + 3) / 4 : 16384)), dim3(256), 0, (hipStream_t)stream,
+                     t, act, ft, x, P, n, {spec.dim_x}, {spec.dim_err * spec.dim_err}, r, kind, nobs, Z, EA, {max(k.zdim for k in spec.kinds)}, {eamax}, o);
+  RN_HIP(hipGetLastError());
+  return rn::OK;
+}}""")
+  hdr.append(f"int {name}_batch_timeline_push({tl_push});")
+
   if hasattr(fam_mod, "launch_maha"):
     for k in spec.kinds:
       abi.append(f"""int {name}_batch_maha_{k.kind}(const double *x, const double *P, const double *z, const double *R, int r_per_filter, const double *ea, int64_t n, double *d2, void *stream) {{

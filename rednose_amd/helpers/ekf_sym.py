@@ -415,6 +415,10 @@ class BatchedEKF:
       rewind_to_keep > 0 -- a late observation rewinds, applies and fast-forwards ONLY the filters it is late for, each
       through its own ring of checkpoints: N independent instances of the reference's orchestrator
       (/root/reference/rednose/helpers/ekf_sym.cc:83-156, ekf_sym.py:418-482), fed from N independent logs.
+      A call in which no active filter is late -- the common one -- does its bookkeeping on the device (device_timeline: None = where
+      the library exports {name}_batch_timeline_plan / _push, False = never, True = required, KalmanError otherwise): filter times
+      and rings stay in HBM, the host reads one integer per call; `filter_time` is then the (N,) tensor the checkpoint kernel writes
+      in place.  A call with a late filter takes the torch path on the same rings.  pf_stats counts the calls of either path.
 
   Compute goes through the generated library's `{name}_batch_*` entry points on the current torch HIP
   stream; torch is used only for device memory and streams.  No GPU / no library => KalmanError.
@@ -423,7 +427,7 @@ class BatchedEKF:
 
   def __init__(self, folder, name, Q, x_initial, P_initial, dim_main, dim_main_err,  # pylint: disable=dangerous-default-value
                N=0, dim_augment=0, dim_augment_err=0, maha_test_kinds=[], quaternion_idxs=[], global_vars=None,
-               max_rewind_age=1.0, logger=logging, batch=1, device=None, rewind_to_keep=0, per_filter=False):
+               max_rewind_age=1.0, logger=logging, batch=1, device=None, rewind_to_keep=0, per_filter=False, device_timeline=None):
     import torch  # pylint: disable=import-outside-toplevel
     if not torch.cuda.is_available():
       raise KalmanError("BatchedEKF needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
@@ -472,6 +476,15 @@ class BatchedEKF:
     if sorted(lib_maha) != sorted(self.maha_test_kinds):
       raise KalmanError(f"library {name} was generated with maha_test_kinds={lib_maha}, constructor got {self.maha_test_kinds}")
 
+    # Per-filter timelines: the in-order bookkeeping of a call (dt = t[i] - ft[i], the late test, the checkpoint) on the device, through
+    # {name}_batch_timeline_plan / _push.  None: where the library has them; False: the torch bookkeeping always; True: required.
+    self._device_timeline = self._has_timeline_abi() if device_timeline is None else bool(device_timeline)
+    if self._device_timeline and not self._has_timeline_abi():
+      raise KalmanError(f"device_timeline=True: lib{name}.so has no {name}_batch_timeline_plan / _push: regenerate it (gen_code) with this version of rednose_amd")
+    self.pf_stats = {"fast": 0, "legacy": 0}      # per-filter calls served by the device timeline / by the torch bookkeeping (late observations: rewind)
+    self._ft_dev = None                # the (N,) tensor of filter times k_timeline_push writes in place (== self.filter_time while it is current)
+    self._tl = None                    # buffers of the device timeline (_timeline_buffers)
+
     self.Q = torch.as_tensor(np.ascontiguousarray(Q, dtype=np.float64), device=self.device)
     self._R_cache = OrderedDict()          # small LRU of shared (Z, Z) noise matrices already on the device
     self.flags = torch.zeros(self.batch, dtype=torch.uint8, device=self.device)
@@ -492,6 +505,9 @@ class BatchedEKF:
   def _p(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
+  def _has_timeline_abi(self):
+    return all(hasattr(self._lib, f"{self.name}_batch_timeline_{s}") for s in ("plan", "push"))
+
   def _dev(self, a, shape=None):
     torch = self._torch
     t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64))
@@ -508,6 +524,7 @@ class BatchedEKF:
     if filter_time is not None and not np.isscalar(filter_time):
       filter_time = self._dev(filter_time, (self.batch,)).clone()     # (N,) per-filter times until the first step
     self.filter_time = filter_time
+    self._ft_dev = None                # (the device timeline re-seeds its times from filter_time)
     self.reset_rewind()
 
   def reset_rewind(self):
@@ -849,9 +866,6 @@ class BatchedEKF:
       raise KeyError(kind)
     if not hasattr(self._lib, f"{self.name}_batch_predict_update_{kind}_masked"):
       raise KalmanError(f"lib{self.name}.so has no masked entry points: regenerate it (gen_code) with this version of rednose_amd")
-    tt = (torch.full((N,), float(t), dtype=torch.float64, device=self.device) if np.isscalar(t) else self._dev(t, (N,)))
-    act = (torch.ones(N, dtype=torch.bool, device=self.device) if active is None
-           else torch.as_tensor(active, device=self.device).to(torch.bool).expand(N).clone())
     multi = (z.ndim if hasattr(z, "ndim") else np.ndim(z)) == 3      # (N, n, Z): n observations per filter in this call
     if multi:
       zl, Rl, per, eal = self._multi_obs(kind, z, R, extra_args)
@@ -862,6 +876,16 @@ class BatchedEKF:
       if isinstance(z, torch.Tensor) and zin.data_ptr() == z.data_ptr() and keep_estimate:
         zin = zin.clone()
       zl, Rl, eal = [zin], [Rd], [self._ea(kind, extra_args)]
+    if self._device_timeline:
+      ret = self._timeline_call(t, active, kind, zl, Rl, per, eal, multi, keep_estimate, extra_args)
+      if ret is not None:
+        self.pf_stats["fast"] += 1
+        return ret[0]
+      t, active = self._keepalive_timeline[0], (None if active is None else self._keepalive_timeline[1])      # (on the device already)
+    self.pf_stats["legacy"] += 1
+    tt = (torch.full((N,), float(t), dtype=torch.float64, device=self.device) if np.isscalar(t) else self._dev(t, (N,)))
+    act = (torch.ones(N, dtype=torch.bool, device=self.device) if active is None
+           else torch.as_tensor(active, device=self.device).to(torch.bool).expand(N).clone())
     z_obs = [zj.clone() for zj in zl] if (self.rewind_to_keep > 0 or keep_estimate) else None       # the kernels overwrite z with the residuals
     ft = self.filter_times()
     self.filter_time = ft
@@ -900,6 +924,91 @@ class BatchedEKF:
     if keep_estimate:
       return est[0], xk_k, est[1], Pk_k, tt, kind, zl[0], z_obs[0], extra_args
     return zl[0]
+
+  # -- the in-order call with its bookkeeping on the device ----------------------------------------------------------
+  # The checkpoint wants the observation as it came and the step overwrites it: True = k_timeline_plan copies it aside (no launch of its
+  # own, a buffer kept from call to call), False = a clone() in front of the step.  Timed by tools/pf_device_timeline_time.py
+  # (profiles/pf_device_timeline_call_times.txt).
+  timeline_plan_copies_z = True
+
+  def _timeline_buffers(self, zdoubles):
+    """What k_timeline_plan writes, kept from call to call (every launch that reads them is on this stream, in front of the next plan):
+    dt (N,), act / late (N,) bytes, the count of late filters -- on the device, and the pinned word it is copied to -- and z_keep, the
+    observation of a single-observation call as it came."""
+    torch = self._torch
+    N, stream = self.batch, self._torch.cuda.current_stream(self.device).cuda_stream
+    b = self._tl
+    if b is None or b["stream"] != stream:
+      b = self._tl = dict(stream=stream, dt=torch.empty(N, dtype=torch.float64, device=self.device),
+                          act=torch.empty(N, dtype=torch.uint8, device=self.device), late=torch.empty(N, dtype=torch.uint8, device=self.device),
+                          n_late=torch.zeros(1, dtype=torch.int32, device=self.device), host=torch.zeros(1, dtype=torch.int32).pin_memory(),
+                          seen=0, z_keep=None)
+      b["host_np"] = b["host"].numpy()
+    if zdoubles and (b["z_keep"] is None or b["z_keep"].numel() < zdoubles):
+      b["z_keep"] = torch.empty(zdoubles, dtype=torch.float64, device=self.device)
+    return b
+
+  def _timeline_call(self, t, active, kind, zl, Rl, per, eal, multi, keep_estimate, extra_args):
+    """One call on per-filter timelines with no late observation, the bookkeeping in two launches around the step: batch_timeline_plan
+    (dt, who steps, who is late; include/rednose_amd_filter.h), the count of late filters read back -- the call's one host round trip
+    -- the `_masked` step with the plan's outputs, batch_timeline_push (ft and the checkpoint).  -> (result,), or None with NOTHING
+    modified when a filter is late: the caller then takes the torch path, whose rewind works on the same rings."""
+    torch = self._torch
+    N, K, n, Z = self.batch, max(self.rewind_to_keep, 0), len(zl), self.zdims[kind]
+    f64 = dict(dtype=torch.float64, device=self.device)
+    if isinstance(t, torch.Tensor) and t.device == self.device and t.dtype == torch.float64 and tuple(t.shape) == (N,) and t.is_contiguous():
+      tt = t
+    else:
+      tt = torch.full((N,), float(t), **f64) if np.isscalar(t) else self._dev(t, (N,))
+    a8 = None
+    if active is not None:
+      a8 = torch.as_tensor(active, device=self.device)
+      a8 = (a8.view(torch.uint8) if a8.dtype == torch.bool else a8.to(torch.bool).view(torch.uint8)).expand(N).contiguous()
+    ft = self.filter_time
+    if ft is None or ft is not self._ft_dev:        # (re-)seeded: init_state, set_filter_time, a call the torch path served
+      ft = self.filter_times()
+      ft = ft.contiguous().clone() if ft is self.filter_time else ft
+      self._ft_dev = self.filter_time = ft
+    copy_z = self.timeline_plan_copies_z and K > 0 and not multi and not keep_estimate
+    b = self._timeline_buffers(N * Z if copy_z else 0)
+    self._call("batch_timeline_plan", self._p(tt), self._p(a8), self._p(ft), N, self._p(b["dt"]), self._p(b["act"]), self._p(b["late"]),
+               self._p(b["n_late"]), self._p(zl[0]) if copy_z else None, self._p(b["z_keep"]) if copy_z else None, N * Z if copy_z else 0, self._stream())
+    b["host"].copy_(b["n_late"], non_blocking=True)
+    torch.cuda.current_stream(self.device).synchronize()
+    count = int(b["host_np"][0])
+    late, b["seen"] = count != b["seen"], count        # (the counter accumulates)
+    if late:
+      self._keepalive_timeline = (tt, a8)
+      return None
+    z_obs = None
+    if copy_z:
+      z_keep, z_sf, z_so = b["z_keep"], Z, 0
+    elif K > 0 or keep_estimate:
+      z_obs = [zj.clone() for zj in zl]                # the kernels overwrite z with the residuals
+      z_keep, z_sf, z_so = (torch.stack(z_obs, 1), n * Z, Z) if n > 1 else (z_obs[0], Z, 0)
+    est = self._masked_step(kind, zl, Rl, per, eal, b["dt"], b["act"], keep_estimate)
+    if K > 0:
+      if self._ring is None or self._ring["nmax"] < n:
+        self._ring_alloc(n)
+      r = self._ring
+      Rk, r_so = (torch.stack(Rl, 0), (N * Z * Z if per else Z * Z)) if n > 1 else (Rl[0], 0)
+      EA = self.eadims.get(kind, 0)
+      eak, ea_so = (None, 0) if EA == 0 else ((torch.stack(eal, 0), N * EA) if n > 1 else (eal[0], 0))
+      self._call("batch_timeline_push", self._p(tt), self._p(b["act"]), self._p(ft), self._p(self.x), self._p(self.P), N, K, r["nmax"],
+                 self._p(r["t"]), self._p(r["x"]), self._p(r["P"]), self._p(r["kind"]), self._p(r["nobs"]), self._p(r["z"]), self._p(r["R"]), self._p(r["ea"]),
+                 self._p(r["head"]), self._p(r["length"]), int(kind), n, self._p(z_keep), z_sf, z_so, self._p(Rk), per, Z * Z, r_so,
+                 self._p(eak), EA, ea_so, self._stream())
+      self._keepalive_timeline = (tt, a8, z_keep, Rk, eak)
+    else:
+      self._call("batch_timeline_push", self._p(tt), self._p(b["act"]), self._p(ft), None, None, N, 0, 0, None, None, None, None, None, None, None, None,
+                 None, None, int(kind), n, None, 0, 0, None, 0, 0, 0, None, 0, 0, self._stream())
+      self._keepalive_timeline = (tt, a8)
+    if not keep_estimate:
+      return (torch.stack(zl, 1) if multi else zl[0],)
+    xk_k, Pk_k = self.x.clone(), self.P.clone()
+    if multi:
+      return ((est[0], xk_k, est[1], Pk_k, tt, kind, list(torch.stack(zl, 1).unbind(1)), torch.stack(z_obs, 1), extra_args),)
+    return ((est[0], xk_k, est[1], Pk_k, tt, kind, zl[0], z_obs[0], extra_args),)
 
   def _ring_alloc(self, nmax=1):
     """Per-filter checkpoint rings in HBM: K entries per filter, an entry = time, state after the call, and the call's observation(s) --

@@ -750,6 +750,131 @@ __global__ void k_flags_set(uint8_t* __restrict__ flags, const uint8_t* __restri
 }
 
 // ------------------------------------------------------------------------------------------------
+// per-filter timelines, the in-order bookkeeping of a call on the device: k_timeline_plan decides before the step what every filter
+// does in this call (its dt, whether it steps, whether its observation is late), k_timeline_push writes the call's checkpoint behind
+// the step.  Between the two the orchestrator reads ONE integer, the number of late filters: zero is the common call.
+// ------------------------------------------------------------------------------------------------
+// One lane per filter, PURE: ft and the rings are only read.  dt_out / act_out are what the `_masked` step entry points take.
+// n_late ACCUMULATES (one vector atomic per wavefront that has a late filter): the caller zeroes it, or compares with the value before.
+// z_keep (may be NULL): z_count doubles of z_src copied aside -- the step overwrites its z with the residuals, the checkpoint wants
+// the observations as they came.
+__global__ __launch_bounds__(256) void k_timeline_plan(const double* __restrict__ t, const uint8_t* __restrict__ active,
+                                                       const double* __restrict__ ft, const int64_t n, double* __restrict__ dt_out,
+                                                       uint8_t* __restrict__ act_out, uint8_t* __restrict__ late_out,
+                                                       int32_t* __restrict__ n_late, const double* __restrict__ z_src,
+                                                       double* __restrict__ z_keep, const int64_t z_count) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  // (bounded by the wavefront's first filter: every lane of a wavefront takes part in the ballot)
+  for (int64_t base = first - (threadIdx.x & (WAVE - 1)); base < n; base += stride) {
+    const int64_t i = base + (threadIdx.x & (WAVE - 1));
+    bool late = false;
+    if (i < n) {
+      const bool on = active == nullptr || active[i] != 0;
+      const double ti = t[i], fi = ft[i];
+      late = on && ti < fi;                      // (false when either is NaN: a filter that has not started adopts t)
+      double dt = 0.0;
+      if (on && !late) {
+        dt = ti - fi;
+        if (dt != dt) dt = 0.0;                                        // torch.nan_to_num, which the orchestrator applied here before
+        else if (dt > 1.7976931348623157e308) dt = 1.7976931348623157e308;
+        else if (dt < -1.7976931348623157e308) dt = -1.7976931348623157e308;
+      }
+      dt_out[i] = dt;
+      act_out[i] = (uint8_t)(on && !late);
+      late_out[i] = (uint8_t)late;
+    }
+    const unsigned long long m = __ballot(late);
+    if (m != 0ull && (threadIdx.x & (WAVE - 1)) == 0) atomicAdd(n_late, (int32_t)__popcll(m));
+  }
+  if (z_keep != nullptr)
+    for (int64_t i = first; i < z_count; i += stride) z_keep[i] = z_src[i];
+}
+
+// `len` doubles, contiguous on both sides, by the lanes of one wavefront: 16 bytes per lane where both sides are 16-byte aligned (rows of x
+// and P are when D / E * E are even, or the record index is), 8 otherwise
+__device__ __forceinline__ void wave_copy(double* __restrict__ dst, const double* __restrict__ src, const int64_t len, const int lane) {
+  if (((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15u) == 0) {
+    const int64_t nv = len >> 1;
+    double2* __restrict__ d2 = reinterpret_cast<double2*>(dst);
+    const double2* __restrict__ s2 = reinterpret_cast<const double2*>(src);
+    for (int64_t i = lane; i < nv; i += WAVE) d2[i] = s2[i];
+    if ((len & 1) && lane == 0) dst[len - 1] = src[len - 1];
+  } else {
+    for (int64_t i = lane; i < len; i += WAVE) dst[i] = src[i];
+  }
+}
+
+// The shape of the rings k_timeline_push writes (BatchedEKF._ring_alloc): K entries per filter, ring arrays t (K, n), x (K, n, D),
+// P (K, n, E, E), kind / nobs (K, n), z (K, n, nmax, zmax), R (K, n, nmax, zmax, zmax), ea (K, n, nmax, eamax), head / length (n)
+struct TimelineRing {
+  int64_t K, nmax;
+  double *t, *x, *P;
+  int32_t *kind, *nobs;
+  double *z, *R, *ea;
+  int64_t *head, *length;
+};
+// The call's observations as they came: observation j of filter f at base + f * stride_f + j * stride_o (stride_f = 0: shared by the filters)
+struct TimelineObs {
+  const double *z, *R, *ea;
+  int64_t z_sf, z_so, r_sf, r_so, ea_sf, ea_so;
+};
+
+// The whole checkpoint of a call in one launch, for the filters with act[f] != 0: ft[f] = t[f], the filter's ring advances by one entry
+// (overwriting its oldest when full) and the entry takes t, x, P, kind, nobs and the call's nobs observations with their noise and
+// extra arguments (EKFSym::checkpoint, ekf_sym.cc:142-156, for n filter instances at once).  One
+// wavefront per filter, four per workgroup, grid-stride; the records of different filters do not meet.  K == 0: only ft.
+__global__ __launch_bounds__(256) void k_timeline_push(const double* __restrict__ t, const uint8_t* __restrict__ act, double* __restrict__ ft,
+                                                       const double* __restrict__ x, const double* __restrict__ P, const int64_t n, const int D,
+                                                       const int EE, const TimelineRing r, const int kind, const int nobs, const int Z,
+                                                       const int EA, const int zmax, const int eamax, const TimelineObs o) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  for (int64_t f = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); f < n; f += (int64_t)gridDim.x * 4) {
+    if (act[f] == 0) continue;
+    const double tf = t[f];
+    if (r.K <= 0) {
+      if (lane == 0) ft[f] = tf;
+      continue;
+    }
+    int64_t head = r.head[f], length = r.length[f];
+    if (head < 0 || head >= r.K) head = 0;                 // (a ring position is never trusted as an address)
+    if (length < 0) length = 0;
+    if (length >= r.K) {
+      length = r.K;
+      head = (head + 1) % r.K;
+    } else {
+      length += 1;
+    }
+    const int64_t e = ((head + length - 1) % r.K) * n + f;      // this entry, in units of one filter's record
+    if (lane == 0) {
+      ft[f] = tf;
+      r.head[f] = head;
+      r.length[f] = length;
+      r.t[e] = tf;
+      r.kind[e] = kind;
+      r.nobs[e] = nobs;
+    }
+    wave_copy(r.x + e * D, x + f * D, D, lane);
+    wave_copy(r.P + e * EE, P + f * EE, EE, lane);
+    double* rz = r.z + e * r.nmax * zmax;
+    double* rR = r.R + e * r.nmax * zmax * zmax;
+    double* rea = r.ea + e * r.nmax * eamax;
+    for (int i = lane; i < nobs * Z; i += WAVE) {
+      const int j = i / Z, c = i - j * Z;
+      rz[j * zmax + c] = o.z[f * o.z_sf + j * o.z_so + c];
+    }
+    for (int i = lane; i < nobs * Z * Z; i += WAVE) {
+      const int j = i / (Z * Z), q = i - j * (Z * Z), row = q / Z, c = q - row * Z;
+      rR[(j * zmax + row) * zmax + c] = o.R[f * o.r_sf + j * o.r_so + q];
+    }
+    for (int i = lane; i < nobs * EA; i += WAVE) {
+      const int j = i / EA, c = i - j * EA;
+      rea[j * eamax + c] = o.ea[f * o.ea_sf + j * o.ea_so + c];
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // host-side staging for the single-filter host-pointer entry points (the reference's scalar ABI)
 // ------------------------------------------------------------------------------------------------
 // One buffer of PINNED host memory mapped into the device's address space: an entry point packs its arguments into `host` with memcpy,
