@@ -287,6 +287,13 @@ __global__ __launch_bounds__(64) void k_augment(double* __restrict__ gx, double*
 }}""")
     hdr.append(f"void {name}_set_{var.name}(double x);")
   from rednose_amd.codegen import tuning as _tn
+  if fam == "small" and _tn.current().small_timeline:      # 256 workgroups x 8 slots x (shader cycles, 100 MHz wall clock)
+    abi.append(f"""int {name}_debug_timeline(unsigned long long *out) {{
+  RN_HIP(hipDeviceSynchronize());
+  RN_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tl), sizeof(unsigned long long) * 256 * 8 * 2, 0, hipMemcpyDeviceToHost));
+  return rn::OK;
+}}""")
+    hdr.append(f"int {name}_debug_timeline(unsigned long long *out);")
   if fam == "wide" and _tn.current().wide_timeline:
     abi.append(f"""int {name}_debug_timeline(unsigned long long *out) {{
   RN_HIP(hipDeviceSynchronize());

@@ -87,8 +87,13 @@ def predict_regs(spec, sym=False):
   return "\n".join([head] + _ind(body) + ["}"]), F
 
 
-def update_regs(spec, k, sym=False):
-  """-> text of `update_<kind>_regs(x, P, z, R)`; returns the gate flag.  sym=True: `update_<kind>_regs_sym`, see predict_regs."""
+def update_regs(spec, k, sym=False, split=False):
+  """-> text of `update_<kind>_regs(x, P, z, R)`; returns the gate flag.  sym=True: `update_<kind>_regs_sym`, see predict_regs.
+
+  split=True (step-granular kernels, tuning knob small_split): `update_<kind>_regs_split(x, P, z, R, mid)` -- the same statements in the same
+  order, but x and the residual are assigned where they are final, between the gain and the Joseph form, and `mid()` is called there: the
+  kernel sends them on their way while the bulk of the update's arithmetic is still to come."""
+  assert not (sym and split)
   D, E, Z = spec.dim_x, spec.dim_err, k.zdim
   names = dict(vector_names(spec.x_sym, 'x'))
   if k.ea_sym is not None:
@@ -143,6 +148,14 @@ def update_regs(spec, k, sym=False):
     eblk.add(f"xi_{i}", sp.Matrix(spec.err_eqs[0])[i])
   estmts, est = eblk.lower()
   b += estmts
+  final = []
+  for i in range(D):
+    kind, val = est[f"xi_{i}"]
+    final.append(f"x[{i}] = xi_{i};" if kind == 'expr' else f"x[{i}] = {float(val)!r};")
+  for i in range(Z):
+    final.append(f"z[{i}] = y_{i};")
+  if split:      # nothing below reads x, z or y: the model's expressions were all evaluated above
+    b += final + ["mid();"]
   # B = P - K G (in place).  sym: B = (I - K He) P is NOT symmetric -- its upper triangle is needed for the result and the
   # columns He touches for C below, all rows of those; an entry below the diagonal starts from its mirror image and lives in the
   # (otherwise unused) lower half of the array until the final mirroring overwrites it.
@@ -173,15 +186,13 @@ def update_regs(spec, k, sym=False):
       b.append(f"P[{i * E + j}] = {chain(f'P[{i * E + j}]', ((f'Dm_{i}_{zi}', K(j, zi)) for zi in range(Z)))};")
   if sym:
     b += [f"P[{j * E + i}] = P[{i * E + j}];" for i in range(E) for j in range(i + 1, E)]
-  for i in range(D):
-    kind, val = est[f"xi_{i}"]
-    b.append(f"x[{i}] = xi_{i};" if kind == 'expr' else f"x[{i}] = {float(val)!r};")
-  for i in range(Z):
-    b.append(f"z[{i}] = y_{i};")
+  if not split:
+    b += final
   b.append("return gated;")
   ea_arg = ", const double* __restrict__ ea" if k.ea_sym is not None else ""
-  head = (f"__device__ __forceinline__ int update_{k.kind}_regs{'_sym' if sym else ''}(double (&x)[{D}], double (&P)[{E * E}], "
-          f"double (&z)[{Z}], const double (&R)[{Z * Z}]{ea_arg}) {{")
+  head = (("template <class Mid>\n" if split else "") +
+          f"__device__ __forceinline__ int update_{k.kind}_regs{'_sym' if sym else ('_split' if split else '')}(double (&x)[{D}], double (&P)[{E * E}], "
+          f"double (&z)[{Z}], const double (&R)[{Z * Z}]{ea_arg}{', Mid&& mid' if split else ''}) {{")
   return "\n".join([head] + _ind(b) + ["}"]), He
 
 
@@ -283,7 +294,8 @@ def norm_text(spec):
 
 def kernels(spec):
   """Device functions + __global__ kernels of family S for every kind."""
-  waves = tuning.current().small_waves
+  tune = tuning.current()
+  waves, zwait, split, tline = tune.small_waves, tune.small_zwait, bool(tune.small_split), bool(tune.small_timeline)
   kattr = f" __attribute__((amdgpu_waves_per_eu({waves}, {waves})))" if waves else ""
   D, E = spec.dim_x, spec.dim_err
   EE = E * E
@@ -292,7 +304,7 @@ def kernels(spec):
     ptxt, _ = predict_regs(spec, sym)
     out.append(ptxt)
     for k in spec.kinds:
-      utxt, _ = update_regs(spec, k, sym)
+      utxt, _ = update_regs(spec, k, sym, split=split and not sym)
       out.append(utxt)
   out.append(f"""
 // the fused multi-step kernels read (P + P^T) / 2 of the caller's covariance, once, as the state enters the registers
@@ -304,7 +316,22 @@ __device__ __forceinline__ void symmetrize_regs(double (&P)[{EE}]) {{
   }}
 }}
 """)
+  out.append("""
+// What the step kernels use of the runtime beyond the tile copies: the counted wait and the per-filter dt as an LDS-DMA transfer
+// (templates/ekf_hip_rt.h).  A host build of this text (the kernels run lane by lane as threads, every copy synchronous) has nothing to wait for.
+#ifdef __HIP__
+template <int EPF> __device__ __forceinline__ void wait_but_tile(int cnt) { rn::async_wait_but_tile<EPF>(cnt); }
+__device__ __forceinline__ void lane_dt_request(const double* g_lane, double* lds, int lane) { (void)lane; rn::lane_double_g2l_async(g_lane, lds); }
+__device__ __forceinline__ double lane_dt(const double* lds, int lane) { return rn::lane_double_from_lds(lds, lane); }
+#else
+template <int EPF> inline void wait_but_tile(int) {}
+inline void lane_dt_request(const double* g_lane, double* lds, int lane) { lds[lane] = *g_lane; }
+inline double lane_dt(const double* lds, int lane) { return lds[lane]; }
+#endif
+""")
   norm = norm_text(spec)
+  if tline:
+    out.append("__device__ unsigned long long g_tl[256 * 8 * 2];      // debug timeline (tuning knob small_timeline)")
 
   out.append(f"""
 // ---- predict only: one launch propagates n filters by dt -------------------------------------------
@@ -355,7 +382,121 @@ __global__ __launch_bounds__(64) void k_predict(double* __restrict__ gx, double*
       kn = f"k_stepc_{k.kind}" if ckpt else f"k_step_{k.kind}"
       cargs = ", double* __restrict__ cx, double* __restrict__ cP, double* __restrict__ cz" if ckpt else ""
       cz_store = f"\n    rn::tile_l2g<{Z}>(cz + base * {Z}, cnt, s_z, lane);      // the observations, before the residuals take their place" if ckpt else ""
-      c_store = f"\n    rn::tile_l2g<{D}>(cx + base * {D}, cnt, s_x, lane);\n    rn::tile_l2g<{EE}>(cP + base * {EE}, cnt, s_P, lane);" if ckpt else ""
+      cx_store = f"\n    rn::tile_l2g<{D}>(cx + base * {D}, cnt, s_x, lane);" if ckpt else ""
+      cP_store = f"\n    rn::tile_l2g<{EE}>(cP + base * {EE}, cnt, s_P, lane);" if ckpt else ""
+
+      tl_pin = f"""
+#pragma unroll
+    for (int i = 0; i < {EE}; i++) rn::pin(P[i]);""" if tline else ""      # stamped builds: a phase's arithmetic ends at its stamp
+
+      def TL(i):      # debug stamps (tuning knob small_timeline; tools/timeline.py small): shader cycles and the 100 MHz wall clock, in scalar registers
+        return f"\n    if (tl_on) {{ tl_c[{i}] = __builtin_readcyclecounter(); tl_w[{i}] = wall_clock64(); }}" if tline else ""
+      act = """
+    // masked-out filters (active[i] == 0) pass through untouched: x, P and z leave as they came, flag bit 4 is set.  The mask is requested
+    // behind the tiles: hipcc turns it into a lane mask at once, i.e. waits for it and for everything in front of it -- one round trip for all
+    uint8_t act = 1;
+    if (active != nullptr) act = active[base + (lane < cnt ? lane : cnt - 1)];"""
+      tile_x = f"rn::tile_g2l_async<{D}>(gx + base * {D}, cnt, s_x, lane);"
+      tile_P = f"rn::tile_g2l_async<{EE}>(gP + base * {EE}, cnt, s_P, lane);"
+      tile_z = f"rn::tile_g2l_async<{Z}>(gz + base * {Z}, cnt, s_z, lane);"
+      tile_R = f"if (r_per_filter) rn::tile_g2l_async<{ZZ}>(gR + base * {ZZ}, cnt, s_R, lane);"
+      # the per-filter dt rides with the tiles (LDS-DMA, clamped inside a ragged tile: a lane without a filter stores nothing)
+      tile_dt = "if (DO_PREDICT && gdt != nullptr) lane_dt_request(gdt + base + (lane < cnt ? lane : cnt - 1), s_dt, lane);"
+      read_dt = "const double dt = (DO_PREDICT && gdt != nullptr) ? lane_dt(s_dt, lane) : dt_scalar;"
+      read_xP = f"""rn::lds_to_regs<{D}>(s_x, lane, x);
+    rn::lds_to_regs<{EE}>(s_P, lane, P);"""
+      read_zR = f"""rn::lds_to_regs<{Z}>(s_z, lane, z);
+    if (r_per_filter) rn::lds_to_regs<{ZZ}>(s_R, lane, R);"""
+      predict = f"""if (DO_PREDICT) {{
+      predict_regs(x, P, s_Q, dt);
+      {norm}
+    }}"""
+      if zwait == 1:
+        # vmcnt retires in issue order, so the tile that may stay in flight goes last: the observations are first read by the update, after
+        # 42 LDS reads and the whole predict; in a stream they are also the slowest tile (a buffer nothing has touched since it was written: HBM,
+        # while x and P were written by the previous launch and sit in the L2 / Infinity Cache)
+        load = f"""{tile_x}
+    {tile_P}
+    {tile_R}
+    {tile_dt}
+    {tile_z}{TL(1)}{act}
+    wait_but_tile<{Z}>(cnt);
+    rn::wave_lds_sync();{TL(2)}
+    double x[{D}], P[{EE}], z[{Z}];
+    {read_dt}
+    {read_xP}
+    {predict}
+    // (the predict's arithmetic ends here: without the pins hipcc sinks it below the wait, into the update's)
+#pragma unroll
+    for (int i = 0; i < {D}; i++) rn::pin(x[i]);
+#pragma unroll
+    for (int i = 0; i < {EE}; i++) rn::pin(P[i]);{TL(4)}
+    rn::async_wait();
+    rn::wave_lds_sync();{TL(3)}{cz_store}
+    {read_zR}"""
+      else:
+        # one wait for all tiles; 0: the observations first (they are the slowest tile, see above), 2: between x and P
+        order = [tile_z, tile_R, tile_x, tile_P] if zwait == 0 else [tile_x, tile_R, tile_z, tile_P]
+        nl = "\n    "
+        tlw = (f"\n    if (tl_on && cnt == 64) rn::async_wait_but<{(32 * D + 63) // 64 + (32 * EE + 63) // 64}>();{TL(3)}" if (tline and zwait == 0) else
+               (f"\n    if (tl_on && cnt == 64) rn::async_wait_but<{(32 * EE + 63) // 64}>();{TL(3)}" if tline else ""))
+        load = f"""{nl.join(order)}
+    {tile_dt}{TL(1)}{act}{tlw}
+    rn::async_wait();
+    rn::wave_lds_sync();{TL(2)}{cz_store}
+    double x[{D}], P[{EE}], z[{Z}];
+    {read_dt}
+    {read_xP}
+    {read_zR}
+    {predict}{tl_pin}{TL(4)}"""
+      flag_acc = f"""double acc = 0.0;
+#pragma unroll
+      for (int i = 0; i < {D}; i++) acc += x[i];
+      if (!(acc - acc == 0.0)) nf = 2;          // non-finite state"""
+      if split:
+        # x and the residual are final before the Joseph form, the bulk of the update's arithmetic: they leave there, P follows alone
+        update = f"""int nf = 0;
+    int fl = update_{k.kind}_regs_split(x, P, z, R{ea}, [&]() {{
+      {norm}
+      rn::wave_lds_sync();
+      if (on) {{
+        rn::regs_to_lds<{D}>(s_x, lane, x);
+        rn::regs_to_lds<{Z}>(s_z, lane, z);
+      }}
+      rn::wave_lds_sync();
+      rn::tile_l2g<{D}>(gx + base * {D}, cnt, s_x, lane);
+      rn::tile_l2g<{Z}>(gz + base * {Z}, cnt, s_z, lane);{cx_store.replace(chr(10) + "    ", chr(10) + "      ")}
+      {flag_acc}
+    }});{tl_pin}{TL(5)}
+    rn::wave_lds_sync();
+    if (on) rn::regs_to_lds<{EE}>(s_P, lane, P);
+    rn::wave_lds_sync();
+    rn::tile_l2g<{EE}>(gP + base * {EE}, cnt, s_P, lane);{cP_store}"""
+      else:
+        update = f"""int nf = 0;
+    int fl = update_{k.kind}_regs(x, P, z, R{ea});
+    {norm}{tl_pin}{TL(5)}
+    rn::wave_lds_sync();
+    if (on) {{
+      rn::regs_to_lds<{D}>(s_x, lane, x);
+      rn::regs_to_lds<{EE}>(s_P, lane, P);
+      rn::regs_to_lds<{Z}>(s_z, lane, z);
+    }}
+    rn::wave_lds_sync();
+    rn::tile_l2g<{D}>(gx + base * {D}, cnt, s_x, lane);
+    rn::tile_l2g<{EE}>(gP + base * {EE}, cnt, s_P, lane);
+    rn::tile_l2g<{Z}>(gz + base * {Z}, cnt, s_z, lane);{cx_store}{cP_store}
+    {{
+      {flag_acc}
+    }}"""
+      tl_decl = f"""
+    const bool tl_on = tile == blockIdx.x && blockIdx.x < 256;
+    unsigned long long tl_c[7] = {{0, 0, 0, 0, 0, 0, 0}}, tl_w[7] = {{0, 0, 0, 0, 0, 0, 0}};{TL(0)}""" if tline else ""
+      tl_out = f"""{TL(6)}
+    if (tl_on && lane == 0) {{
+#pragma unroll
+      for (int i = 0; i < 7; i++) {{ g_tl[(blockIdx.x * 8 + i) * 2] = tl_c[i]; g_tl[(blockIdx.x * 8 + i) * 2 + 1] = tl_w[i]; }}
+    }}""" if tline else ""
       out.append(f"""
 // ---- kind {k.kind}: [predict +] update{" + checkpoint" if ckpt else ""}, state round-trips HBM once per launch --------------------------
 template <bool DO_PREDICT>
@@ -368,6 +509,7 @@ __global__ __launch_bounds__(64){kattr} void {kn}(double* __restrict__ gx, doubl
   __shared__ __attribute__((aligned(16))) double s_z[64 * {Z | 1}];
   __shared__ __attribute__((aligned(16))) double s_R[64 * {ZZ | 1}];
   __shared__ __attribute__((aligned(16))) double s_Q[{EE}];
+  __shared__ __attribute__((aligned(16))) double s_dt[64];
   const int lane = threadIdx.x;
   if (DO_PREDICT) {{
     for (int i = lane; i < {EE}; i += 64) s_Q[i] = gQ[i];
@@ -375,52 +517,18 @@ __global__ __launch_bounds__(64){kattr} void {kn}(double* __restrict__ gx, doubl
   const int64_t tiles = (n + 63) >> 6;
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {{
     const int64_t base = tile << 6;
-    const int cnt = (n - base) < 64 ? (int)(n - base) : 64;
-    // the observations first: in a stream every launch reads a z buffer nothing has touched since it was written (HBM), while x and P
-    // were written by the previous launch and sit in the L2 / Infinity Cache -- the tile waits for its slowest load
-    rn::tile_g2l_async<{Z}>(gz + base * {Z}, cnt, s_z, lane);
-    if (r_per_filter) rn::tile_g2l_async<{ZZ}>(gR + base * {ZZ}, cnt, s_R, lane);
-    rn::tile_g2l_async<{D}>(gx + base * {D}, cnt, s_x, lane);
-    rn::tile_g2l_async<{EE}>(gP + base * {EE}, cnt, s_P, lane);
-    double dt = dt_scalar;
-    if (DO_PREDICT && gdt != nullptr && lane < cnt) dt = gdt[base + lane];
-    rn::async_wait();
-    rn::wave_lds_sync();{cz_store}
-    double x[{D}], P[{EE}], z[{Z}], R[{ZZ}];
-    rn::lds_to_regs<{D}>(s_x, lane, x);
-    rn::lds_to_regs<{EE}>(s_P, lane, P);
-    rn::lds_to_regs<{Z}>(s_z, lane, z);
-    if (r_per_filter) {{
-      rn::lds_to_regs<{ZZ}>(s_R, lane, R);
-    }} else {{
+    const int cnt = (n - base) < 64 ? (int)(n - base) : 64;{tl_decl}
+    // a shared R is requested in front of the tiles and first used behind the wait for all of them: an ordinary load, and at the first
+    // use of one hipcc waits for everything in flight
+    double R[{ZZ}];
+    if (!r_per_filter) {{
 #pragma unroll
       for (int i = 0; i < {ZZ}; i++) R[i] = gR[i];
     }}
-    if (DO_PREDICT) {{
-      predict_regs(x, P, s_Q, dt);
-      {norm}
-    }}
-    int fl = update_{k.kind}_regs(x, P, z, R{ea});
-    {norm}
-    rn::wave_lds_sync();
-    // masked-out filters (active[i] == 0) pass through untouched: x, P and z leave as they came, flag bit 4 is set
-    const bool on = active == nullptr || (lane < cnt && active[base + lane] != 0);
-    if (on) {{
-      rn::regs_to_lds<{D}>(s_x, lane, x);
-      rn::regs_to_lds<{EE}>(s_P, lane, P);
-      rn::regs_to_lds<{Z}>(s_z, lane, z);
-    }}
-    rn::wave_lds_sync();
-    rn::tile_l2g<{D}>(gx + base * {D}, cnt, s_x, lane);
-    rn::tile_l2g<{EE}>(gP + base * {EE}, cnt, s_P, lane);
-    rn::tile_l2g<{Z}>(gz + base * {Z}, cnt, s_z, lane);{c_store}
-    if (flags != nullptr && lane < cnt) {{
-      double acc = 0.0;
-#pragma unroll
-      for (int i = 0; i < {D}; i++) acc += x[i];
-      if (!(acc - acc == 0.0)) fl |= 2;          // non-finite state
-      flags[base + lane] = (uint8_t)(on ? fl : 16);
-    }}
+    {load}
+    const bool on = active == nullptr || (lane < cnt && act != 0);
+    {update}
+    if (flags != nullptr && lane < cnt) flags[base + lane] = (uint8_t)(on ? (fl | nf) : 16);{tl_out}
     rn::wave_lds_sync();
   }}
 }}

@@ -13,6 +13,10 @@ variants do not overwrite generated/).  What each alternative measured: profiles
   wide_lean_q  1 = the lean predict takes its column of Q from registers instead of an LDS copy
   small_waves  amdgpu_waves_per_eu on the lane-per-filter step kernels
   small_max_e  largest error-state count served lane-per-filter
+  small_zwait  tile order / waits of the lane-per-filter step kernels: 1 = x, P, z with a counted wait (the observation tile stays in flight under
+               the predict), 2 = x, z, P and one wait, 0 = z, x, P and one wait
+  small_split  1 = x and the residual leave the lane-per-filter step kernels between the gain and the Joseph form, 0 = with P at the end
+  small_timeline  debug: phase stamps of the lane-per-filter step kernels, read back by {name}_debug_timeline (tools/timeline.py small)
   nt_trace     1 = nontemporal stores for the fused run's covariance trace (lane-group models)
   run_block    steps per block of the lane-per-filter fused run without trace (0 = auto by model size, -1 = that kernel is not emitted)
   exact_math   1 = IEEE division / square root and ocml sin / cos in place of the fast primitives (reference build for the accuracy tests; full sin / cos range)
@@ -39,6 +43,10 @@ class Tuning:
   wide_lean_q: int = 0
   small_waves: int = 0
   small_max_e: int = 7
+  small_zwait: int = 1
+  small_split: int = 1
+  small_timeline: int = 0    # debug: lane 0 of the first 256 workgroups keeps s_memtime / the 100 MHz wall clock of seven phase boundaries of k_step / k_stepc
+                             # in scalar registers and stores them when the tile is done (no store is in flight while a phase is timed)
   run_block: int = 0
   run2_prio: int = 0              # (measured: 20.5-20.9 ms per config-4 chunk at 3 against 20.4 at 0 -- the scalar wavefront is not on the critical path)
   run2: int = 1              # fused run with a scalar wavefront beside the matrix wavefront (emit_run2: two wavefronts per SIMD); 0 = emit_wide3's k_run

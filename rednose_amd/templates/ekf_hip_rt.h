@@ -381,6 +381,43 @@ __device__ __forceinline__ void tile_g2l_async(const double* __restrict__ g, int
 #endif
 }
 
+// Counted wait: at most N vector-memory operations of this wavefront are still in flight.  vmcnt retires in issue order, so everything
+// issued before the last N has completed.  (gfx9 encoding of the s_waitcnt operand: vmcnt in bits 3:0 and 15:14, expcnt 6:4, lgkmcnt 11:8.)
+template <int N>
+__device__ __forceinline__ void async_wait_but() {
+  static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
+  __builtin_amdgcn_s_waitcnt(0x0F70 | (N & 15) | ((N >> 4) << 14));
+}
+
+// global_load_lds instructions tile_g2l_async<EPF> issues for a full tile
+template <int EPF>
+__device__ __forceinline__ constexpr int tile_async_loads() { return (32 * EPF + WAVE - 1) / WAVE; }
+
+// Everything issued before the LAST tile_g2l_async<EPF> has landed; that tile may still be in flight (async_wait() before it is read).
+// A ragged tile went through registers, with the compiler's own waits: nothing counted is in flight behind it, so everything is waited for.
+template <int EPF>
+__device__ __forceinline__ void async_wait_but_tile(int cnt) {
+#if RN_LDS_PAD
+  (void)cnt;
+  async_wait();
+#else
+  if (cnt == WAVE) async_wait_but<tile_async_loads<EPF>()>(); else async_wait();
+#endif
+}
+
+// One double per lane, HBM -> LDS without a register in between (an ordinary load would make hipcc wait for vmcnt(0) at its first use, i.e.
+// for every tile in flight): two 4-byte transfers, low words to the 64 words at `lds`, high words to the 64 behind them.  Any 8-byte aligned
+// source.  lane_double_from_lds() after async_wait / async_wait_but + wave_lds_sync.
+__device__ __forceinline__ void lane_double_g2l_async(const double* __restrict__ g_lane, double* lds) {
+  const char* p = reinterpret_cast<const char*>(g_lane);
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)p, lds_offset_ptr(lds), 4, 0, 0);
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p + 4), lds_offset_ptr(lds + WAVE / 2), 4, 0, 0);
+}
+__device__ __forceinline__ double lane_double_from_lds(const double* lds, int lane) {
+  const int* w = reinterpret_cast<const int*>(lds);
+  return __hiloint2double(w[WAVE + lane], w[lane]);
+}
+
 // lane-per-filter register <-> LDS (filter `lane` owns lds[lane*STR .. lane*STR+EPF), STR = lds_stride<EPF>())
 template <int EPF>
 __device__ __forceinline__ void lds_to_regs(const double* lds, int lane, double (&r)[EPF]) {

@@ -178,7 +178,51 @@ def run():
       prev = m
 
 
+def small():
+  """Phase timeline of the lane-per-filter fused step kernel (k_step_1<true> of kinematic6; tuning knob small_timeline), averaged over the
+  first 256 workgroups, for the two streams of profiles/tuning_notes.md (round 4, stages 4 and 5): every step with an observation buffer
+  of its own that nothing has touched since it was written, and one buffer reused by every step.
+
+    RN_TUNE=small_timeline=1[,small_zwait=..,small_split=..] RN_GEN_DIR=/some/dir python tools/timeline.py small [batch]"""
+  import torch
+  from examples import ensure_generated, GENERATED_DIR
+  from examples.kinematic6_kf import Kinematic6Kalman as K6
+  from rednose_amd.helpers.ekf_sym import BatchedEKF
+  n = int(sys.argv[2]) if len(sys.argv) > 2 else 65536
+  gen = GENERATED_DIR if os.environ.get("RN_NO_GEN") else ensure_generated(["kinematic6"], folder=GENERATED_DIR)
+  f = BatchedEKF(gen, "kinematic6", K6.Q, K6.initial_x, np.diag(K6.initial_P_diag), 6, 6, batch=n)
+  tl = getattr(f._lib, "kinematic6_debug_timeline")
+  g = torch.Generator(device="cuda").manual_seed(0)
+  step = f.bind_step(1, K6.obs_noise[1])
+  steps = 400
+  names = ["entry", "tile loads issued", "x / P arrived", "z arrived", "predict done", "update done", "stores issued"]
+  buf = (ctypes.c_ulonglong * (256 * 8 * 2))()
+  for mode in ("fresh buffer per step", "one reused buffer"):
+    f.init_state(np.tile(K6.initial_x, (n, 1)), np.diag(K6.initial_P_diag), None)
+    zs = [torch.randn((n, 3), dtype=torch.float64, device=f.device, generator=g) for _ in range(steps if mode.startswith("fresh") else 1)]
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for i in range(steps):
+      step(zs[i % len(zs)], 0.01)
+    e1.record()
+    torch.cuda.synchronize()
+    assert tl(ctypes.cast(buf, ctypes.c_void_p)) == 0
+    a = np.frombuffer(buf, dtype=np.uint64).reshape(256, 8, 2).astype(np.float64)[:min(256, (n + 63) // 64), :7]
+    wall, cyc = a[:, :, 1] / 100.0, a[:, :, 0]
+    rate = (cyc[:, 6] - cyc[:, 0]).mean() / max(1e-9, (wall[:, 6] - wall[:, 0]).mean())      # shader cycles per microsecond
+    rel = (cyc - cyc[:, :1]) / rate
+    print(f"--- k_step_1<true>, kinematic6, {n} filters, {mode}: {e0.elapsed_time(e1) * 1e3 / steps:.2f} us per stamped launch; "
+          f"last launch, {a.shape[0]} workgroups, start spread {wall[:, 0].max() - wall[:, 0].min():.2f} us, {rate:.0f} cycles/us")
+    for i in np.argsort(rel.mean(axis=0), kind="stable"):
+      v = rel[:, i]
+      print(f"  {names[i]:20s} {v.mean():7.3f} us   min {v.min():6.3f}  median {np.median(v):6.3f}  max {v.max():6.3f}")
+
+
 if __name__ == "__main__":
+  if len(sys.argv) > 1 and sys.argv[1] == "small":
+    small()
+    sys.exit(0)
   if len(sys.argv) > 1 and sys.argv[1] == "rts":
     rts()
     sys.exit(0)
