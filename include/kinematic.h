@@ -29,6 +29,10 @@ int kinematic_batch_ring_copy(double *ring, int64_t ring_stride, double *flat, i
 int kinematic_batch_flags_set(uint8_t *flags, const uint8_t *mask, int value, int64_t n, void *stream);
 int kinematic_batch_timeline_plan(const double *t, const uint8_t *active, const double *ft, int64_t n, double *dt_out, uint8_t *act_out, uint8_t *late_out, int32_t *n_late, const double *z_src, double *z_keep, int64_t z_count, void *stream);
 int kinematic_batch_timeline_push(const double *t, const uint8_t *act, double *ft, const double *x, const double *P, int64_t n, int64_t K, int64_t nmax, double *ring_t, double *ring_x, double *ring_P, int32_t *ring_kind, int32_t *ring_nobs, double *ring_z, double *ring_R, double *ring_ea, int64_t *ring_head, int64_t *ring_length, int kind, int nobs, const double *z_obs, int64_t z_stride_f, int64_t z_stride_o, const double *R, int r_per_filter, int64_t r_stride_f, int64_t r_stride_o, const double *ea, int64_t ea_stride_f, int64_t ea_stride_o, void *stream);
+int kinematic_has_step_kinds(void);
+int kinematic_batch_predict_update_kinds(double *x, double *P, const double *Q, const double *dt_vec, double dt, const int32_t *kinds, double *z, const double *R, int r_per_filter, int64_t n, int norm_quats, uint8_t *flags, const uint8_t *active, void *stream);
+int kinematic_batch_update_kinds(double *x, double *P, const int32_t *kinds, double *z, const double *R, int r_per_filter, int64_t n, int norm_quats, uint8_t *flags, const uint8_t *active, void *stream);
+int kinematic_batch_timeline_push_kinds(const double *t, const uint8_t *act, double *ft, const double *x, const double *P, int64_t n, int64_t K, int64_t nmax, double *ring_t, double *ring_x, double *ring_P, int32_t *ring_kind, int32_t *ring_nobs, double *ring_z, double *ring_R, double *ring_ea, int64_t *ring_head, int64_t *ring_length, const int32_t *kinds, const double *z_obs, const double *R, int r_per_filter, void *stream);
 int kinematic_batch_maha_1(const double *x, const double *P, const double *z, const double *R, int r_per_filter, const double *ea, int64_t n, double *d2, void *stream);
 void kinematic_msckf_dims(int *dims);
 int kinematic_kind_eadim(int kind);

@@ -261,6 +261,37 @@ extern "C" {
                                        int64_t r_stride_f, int64_t r_stride_o, const double *ea,                  \
                                        int64_t ea_stride_f, int64_t ea_stride_o, void *stream);
 
+/* A DIFFERENT OBSERVATION KIND PER FILTER IN ONE LAUNCH.  N independent filters receive, at a tick, whatever kind their sensor produced
+ * (updates.at(kind), /root/reference/rednose/helpers/ekf_sym.cc:196-219); with the per-kind entry points such a tick is one `_masked`
+ * launch per kind present, each moving the state of ALL filters through HBM.  Here filter i gets predict(dt[i]) and the update of
+ * kinds[i] in one launch: the arithmetic of batch_predict_update_{kinds[i]}_masked, the state crossing HBM once.
+ *   {name}_has_step_kinds() == 1: the library has the kernel.  0: MSCKF models, models with a kind that takes extra arguments or has 7 or
+ *   more rows, or a kernel that did not fit the register file -- the three entry points then return status 4 and nothing is launched.
+ * Buffers (DEVICE, 16-byte aligned like everywhere): kinds (n) int32; z (n, zmax), zmax = {name}_zmax(): the first Z entries of row i are
+ * read and overwritten by the residual, the rest of the row passes through bit for bit; R: r_per_filter != 0 -> (n, zmax * zmax), the
+ * leading Z * Z entries of row i are filter i's row-major R (batch_run's convention); r_per_filter == 0 -> a table (num_kinds, zmax * zmax)
+ * with one such row per kind in the order of {name}_kinds(); dt_vec / dt, active, flags, norm_quats as in the `_masked` entry points.
+ * Per filter: active[i] == 0 -> x, P and the z row untouched, flag 16; active and kinds[i] a kind of the model -> stepped, flags as the
+ * per-kind entry points; active and any other kinds[i] -> untouched like an inactive filter (no predict either), flag 8.
+ * batch_timeline_push_kinds is batch_timeline_push for such a call: kinds (n) in place of (kind, nobs) -- one observation per filter, an
+ * entry that is not a kind of the model skips its filter --, z_obs (n, zmax) the observations as they came, R as above. */
+#define RN_DECLARE_BATCH_KINDS(name)                                                                             \
+  int RN_FN(name, has_step_kinds)(void);                                                                         \
+  int RN_FN(name, batch_predict_update_kinds)(double *x, double *P, const double *Q, const double *dt_vec,        \
+                                              double dt, const int32_t *kinds, double *z, const double *R,        \
+                                              int r_per_filter, int64_t n, int norm_quats, uint8_t *flags,        \
+                                              const uint8_t *active, void *stream);                               \
+  int RN_FN(name, batch_update_kinds)(double *x, double *P, const int32_t *kinds, double *z, const double *R,     \
+                                      int r_per_filter, int64_t n, int norm_quats, uint8_t *flags,                \
+                                      const uint8_t *active, void *stream);                                       \
+  int RN_FN(name, batch_timeline_push_kinds)(const double *t, const uint8_t *act, double *ft, const double *x,    \
+                                             const double *P, int64_t n, int64_t K, int64_t nmax, double *ring_t, \
+                                             double *ring_x, double *ring_P, int32_t *ring_kind,                  \
+                                             int32_t *ring_nobs, double *ring_z, double *ring_R, double *ring_ea, \
+                                             int64_t *ring_head, int64_t *ring_length, const int32_t *kinds,      \
+                                             const double *z_obs, const double *R, int r_per_filter,              \
+                                             void *stream);
+
 #define RN_DECLARE_BATCH_KIND_MASKED(name, k)                                                                   \
   int RN_FN(name, batch_update_##k##_masked)(double *x, double *P, double *z, const double *R, int r_per_filter,  \
                                              const double *ea, int64_t n, int norm_quats, uint8_t *flags,         \

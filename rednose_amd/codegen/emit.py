@@ -35,7 +35,10 @@ SMALL_MAX_E = 7    # lane-per-filter register budget: x, P and the update's temp
 #   no_run2            the fused run with a scalar wavefront beside the matrix wavefront (emit_run2, two wavefronts per SIMD) spilled -> k_run (emit_wide3)
 #   no_run             the fused multi-step run of a model above 32 error states touches scratch -> library without batch_run
 #                      (status ERR_UNSUPPORTED, the step-granular entry points cover such models)
-FALLBACKS = ("force_wide", "no_model_defaults", "no_rts4", "rts_one_wave", "no_rts", "no_run2", "no_run", "no_run_blk", "no_tri")
+#   no_kinds           the mixed-kind step kernel (k_kinds: a kind per filter in one launch) touches scratch memory or spills -> library without
+#                      it ({name}_has_step_kinds() == 0, its entry points return ERR_UNSUPPORTED; one `_masked` launch per kind serves such a call)
+FALLBACKS = ("force_wide", "no_model_defaults", "no_rts4", "rts_one_wave", "no_rts", "no_run2", "no_run", "no_run_blk", "no_tri", "no_kinds")
+KINDS_MAX = 16      # kinds of a model with a mixed-kind step: the Z table rn::k_timeline_push takes by value
 _active = frozenset()      # fallbacks of the emit() call in progress
 
 
@@ -47,6 +50,16 @@ def family(spec, fallbacks=None):
     return "wide"
   from rednose_amd.codegen import tuning
   return "small" if spec.dim_err <= min(SMALL_MAX_E, tuning.current().small_max_e) else "wide"
+
+
+def step_kinds(spec, fallbacks=None):
+  """Does this library get the mixed-kind step kernel k_kinds?  Not MSCKF models, and not models with a kind that takes extra arguments or
+  keeps its innovation covariance in LDS (emit_wide2.WIDE_Z_LDS): those kinds have per-kind buffers the mixed kernel does not carry."""
+  from rednose_amd.codegen import emit_wide2
+  fb = _active if fallbacks is None else fallbacks
+  if "no_kinds" in fb or spec.N > 0 or len(spec.kinds) > KINDS_MAX:
+    return False
+  return all(k.ea_sym is None and k.He_sym is None and k.zdim < emit_wide2.WIDE_Z_LDS and k.kind > 0 for k in spec.kinds)
 
 
 def _align2(n):
@@ -132,13 +145,15 @@ def _emit(spec):
         launch_predict=emit_wide2.launch_predict, launch_step=emit_wide2.launch_step, launch_step_ckpt=emit_wide2.launch_step_ckpt,
         launch_run=emit_run2.launch_run if use_run2 else emit_wide3.launch_run,
         launch_maha=emit_wide2.launch_maha)
+    fam_mod.launch_kinds = emit_wide2.launch_kinds
   else:
     use_tri = False
     fam_mod = types.SimpleNamespace(
       kernels=lambda sp_: emit_small.kernels(sp_) + "\n" + emit_small.maha_kernels(sp_),
       launch_predict=emit_small.launch_predict, launch_step=emit_small.launch_step, launch_step_ckpt=emit_small.launch_step_ckpt,
       launch_run=lambda: emit_small.launch_run(spec),
-      launch_maha=emit_small.launch_maha)
+      launch_maha=emit_small.launch_maha, launch_kinds=emit_small.launch_kinds)
+  has_kinds = step_kinds(spec)
 
   hdr = ["#pragma once", "#include <stdint.h>", "#ifdef __cplusplus", 'extern "C" {', "#endif"]
   src = [f"// GENERATED by rednose_amd.helpers.ekf_sym.gen_code for filter '{name}' -- do not edit.",
@@ -417,11 +432,52 @@ int {name}_batch_predict_update_{k.kind}{sfx}(double *x, double *P, const double
   }}
   if (n == 0) return rn::OK;
   hipLaunchKernelGGL(rn::k_timeline_push, dim3((unsigned)((n + 3) / 4 < 16384 ? (n + 3) / 4 : 16384)), dim3(256), 0, (hipStream_t)stream,
-                     t, act, ft, x, P, n, {spec.dim_x}, {spec.dim_err * spec.dim_err}, r, kind, nobs, Z, EA, {max(k.zdim for k in spec.kinds)}, {eamax}, o);
+                     t, act, ft, x, P, n, {spec.dim_x}, {spec.dim_err * spec.dim_err}, r, kind, nobs, Z, EA, {max(k.zdim for k in spec.kinds)}, {eamax}, o, rn::TimelineKinds{{}});
   RN_HIP(hipGetLastError());
   return rn::OK;
 }}""")
   hdr.append(f"int {name}_batch_timeline_push({tl_push});")
+
+  # A kind per filter in one launch (k_kinds): the step of a call on per-filter timelines in which the filters bring different kinds, and the
+  # checkpoint of such a call.  The symbols exist in every library; without the kernel they return ERR_UNSUPPORTED.
+  zmax_ = max(k.zdim for k in spec.kinds)
+  abi.append(f"int {name}_has_step_kinds(void) {{ return {int(has_kinds)}; }}")
+  hdr.append(f"int {name}_has_step_kinds(void);")
+  no_kinds = ('  return rn::fail(rn::ERR_UNSUPPORTED, 0, "mixed-kind step: not generated for this model (MSCKF model, a kind with extra arguments or a wide '
+              'observation, or the kernel did not fit the register file)", __LINE__);')
+  kinds_pu = ("double *x, double *P, const double *Q, const double *dt_vec, double dt, const int32_t *kinds, double *z, const double *R, int r_per_filter, "
+              "int64_t n, int norm_quats, uint8_t *flags, const uint8_t *active, void *stream")
+  kinds_u = ("double *x, double *P, const int32_t *kinds, double *z, const double *R, int r_per_filter, int64_t n, int norm_quats, uint8_t *flags, "
+             "const uint8_t *active, void *stream")
+  for sym, sig, req, do_p in (("batch_predict_update_kinds", kinds_pu, "x && P && Q && kinds && z && R", True), ("batch_update_kinds", kinds_u, "x && P && kinds && z && R", False)):
+    body = f"""  RN_REQUIRE(n >= 0 && {req}, rn::ERR_ARG);
+  if (n == 0) return rn::OK;
+  RN_REQUIRE(rn::aligned16(x) && rn::aligned16(P) && rn::aligned16(z) && (!r_per_filter || rn::aligned16(R)), rn::ERR_ALIGN);
+{fam_mod.launch_kinds(do_p)}
+  RN_HIP(hipGetLastError());
+  return rn::OK;""" if has_kinds else no_kinds
+    abi.append(f"int {name}_{sym}({sig}) {{\n{body}\n}}")
+    hdr.append(f"int {name}_{sym}({sig});")
+  tl_push_k = ("const double *t, const uint8_t *act, double *ft, const double *x, const double *P, int64_t n, int64_t K, int64_t nmax, "
+               "double *ring_t, double *ring_x, double *ring_P, int32_t *ring_kind, int32_t *ring_nobs, double *ring_z, double *ring_R, double *ring_ea, "
+               "int64_t *ring_head, int64_t *ring_length, const int32_t *kinds, const double *z_obs, const double *R, int r_per_filter, void *stream")
+  tab = ", ".join(f"{{{k.kind}, {k.zdim}}}" for k in spec.kinds)
+  body = f"""  RN_REQUIRE(n >= 0 && K >= 0 && t && act && ft && kinds, rn::ERR_ARG);
+  rn::TimelineRing r{{}};
+  rn::TimelineObs o{{}};
+  if (K > 0) {{
+    RN_REQUIRE(nmax >= 1 && x && P && ring_t && ring_x && ring_P && ring_kind && ring_nobs && ring_z && ring_R && ring_ea && ring_head && ring_length && z_obs && R, rn::ERR_ARG);
+    r = rn::TimelineRing{{K, nmax, ring_t, ring_x, ring_P, ring_kind, ring_nobs, ring_z, ring_R, ring_ea, ring_head, ring_length}};
+    o = rn::TimelineObs{{z_obs, R, nullptr, {zmax_}, 0, r_per_filter ? {zmax_ * zmax_} : 0, 0, 0, 0}};
+  }}
+  if (n == 0) return rn::OK;
+  const rn::TimelineKinds tk{{kinds, {len(spec.kinds)}, {{{tab}}}}};
+  hipLaunchKernelGGL(rn::k_timeline_push, dim3((unsigned)((n + 3) / 4 < 16384 ? (n + 3) / 4 : 16384)), dim3(256), 0, (hipStream_t)stream,
+                     t, act, ft, x, P, n, {spec.dim_x}, {spec.dim_err * spec.dim_err}, r, 0, 1, 0, 0, {zmax_}, {eamax}, o, tk);
+  RN_HIP(hipGetLastError());
+  return rn::OK;""" if has_kinds else no_kinds
+  abi.append(f"int {name}_batch_timeline_push_kinds({tl_push_k}) {{\n{body}\n}}")
+  hdr.append(f"int {name}_batch_timeline_push_kinds({tl_push_k});")
 
   if hasattr(fam_mod, "launch_maha"):
     for k in spec.kinds:

@@ -533,12 +533,138 @@ __global__ __launch_bounds__(64){kattr} void {kn}(double* __restrict__ gx, doubl
   }}
 }}
 """)
+  from rednose_amd.codegen import emit as _emit
+  if _emit.step_kinds(spec):
+    out.append(kinds_kernel(spec, norm, kattr, split))
   if run_block(spec) > 0:          # blocked fused runs: k_run_blk (no trace) and k_run_blk_tr (filtered trace)
     out.append(run_kernel_blk(spec, norm))
     out.append(run_kernel_blk(spec, norm, trace=True))
   else:                            # fallback "no_run_blk" (the blocked kernels spilled): the step-at-a-time k_run serves both
     out.append(run_kernel(spec, norm))
   return "\n".join(out)
+
+
+def kinds_kernel(spec, norm, kattr="", split=False):
+  """k_kinds: the step kernel in which every filter brings its own observation kind (kinds[i]).  The tile is loaded once -- z rows and per-filter
+  R at the strides of the fused run, zmax and zmax^2 --, predicted once, and a per-lane switch over the model's kinds calls update_{k}_regs:
+  a wavefront pays the sum of the kinds present among its 64 filters in arithmetic, and one trip through HBM.  A filter that is masked out, or
+  whose kind the model does not have, is not written back (flags 16 / 8): its lane leaves the LDS image as it was loaded.
+  The load order is that of small_zwait == 1 (z last, counted wait) whatever the knob says -- the knob's alternatives exist for the per-kind
+  kernels' A/B runs only --, s_R is allocated whether or not R comes per filter, and a shared R is read from the table inside the switch (one
+  load per kind present in the wavefront).  This family's kernel is covered by tests; its time has not been measured."""
+  D, E = spec.dim_x, spec.dim_err
+  EE = E * E
+  zmax = max(k.zdim for k in spec.kinds)
+  ZZ = zmax * zmax
+  cases = []
+  for idx, k in enumerate(spec.kinds):
+    Z = k.zdim
+    call = (f"update_{k.kind}_regs_split(x, P, zk, Rk, []() {{}})" if split else f"update_{k.kind}_regs(x, P, zk, Rk)")
+    cases.append(f"""        case {k.kind}: {{
+          double zk[{Z}], Rk[{Z * Z}];
+#pragma unroll
+          for (int i = 0; i < {Z}; i++) zk[i] = z[i];
+          if (r_per_filter) {{
+#pragma unroll
+            for (int i = 0; i < {Z * Z}; i++) Rk[i] = Rf[i];
+          }} else {{
+#pragma unroll
+            for (int i = 0; i < {Z * Z}; i++) Rk[i] = gR[{idx * ZZ} + i];
+          }}
+          fl = {call};
+#pragma unroll
+          for (int i = 0; i < {Z}; i++) z[i] = zk[i];
+          break;
+        }}""")
+  nl = chr(10)
+  return f"""
+// ---- a kind per filter: [predict +] update of kinds[i], state round-trips HBM once per launch whatever the mix of kinds ------------
+template <bool DO_PREDICT>
+__global__ __launch_bounds__(64){kattr} void k_kinds(double* __restrict__ gx, double* __restrict__ gP,
+    double* __restrict__ gz, const double* __restrict__ gR, const int r_per_filter, const int32_t* __restrict__ gkinds,
+    const double* __restrict__ gQ, const double* __restrict__ gdt, const double dt_scalar, const int64_t n,
+    const int norm_quats, uint8_t* __restrict__ flags, const uint8_t* __restrict__ active) {{
+  __shared__ __attribute__((aligned(16))) double s_x[64 * {D | 1}];
+  __shared__ __attribute__((aligned(16))) double s_P[64 * {EE | 1}];
+  __shared__ __attribute__((aligned(16))) double s_z[64 * {zmax | 1}];
+  __shared__ __attribute__((aligned(16))) double s_R[64 * {ZZ | 1}];
+  __shared__ __attribute__((aligned(16))) double s_Q[{EE}];
+  __shared__ __attribute__((aligned(16))) double s_dt[64];
+  const int lane = threadIdx.x;
+  if (DO_PREDICT) {{
+    for (int i = lane; i < {EE}; i += 64) s_Q[i] = gQ[i];
+  }}
+  const int64_t tiles = (n + 63) >> 6;
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {{
+    const int64_t base = tile << 6;
+    const int cnt = (n - base) < 64 ? (int)(n - base) : 64;
+    rn::tile_g2l_async<{D}>(gx + base * {D}, cnt, s_x, lane);
+    rn::tile_g2l_async<{EE}>(gP + base * {EE}, cnt, s_P, lane);
+    if (r_per_filter) rn::tile_g2l_async<{ZZ}>(gR + base * {ZZ}, cnt, s_R, lane);
+    if (DO_PREDICT && gdt != nullptr) lane_dt_request(gdt + base + (lane < cnt ? lane : cnt - 1), s_dt, lane);
+    rn::tile_g2l_async<{zmax}>(gz + base * {zmax}, cnt, s_z, lane);
+    // the mask and the kinds are requested behind the tiles: one round trip for all (see k_step_*)
+    uint8_t act = 1;
+    if (active != nullptr) act = active[base + (lane < cnt ? lane : cnt - 1)];
+    const int kind = gkinds[base + (lane < cnt ? lane : cnt - 1)];
+    wait_but_tile<{zmax}>(cnt);
+    rn::wave_lds_sync();
+    double x[{D}], P[{EE}], z[{zmax}], Rf[{ZZ}];
+    const double dt = (DO_PREDICT && gdt != nullptr) ? lane_dt(s_dt, lane) : dt_scalar;
+    rn::lds_to_regs<{D}>(s_x, lane, x);
+    rn::lds_to_regs<{EE}>(s_P, lane, P);
+    if (DO_PREDICT) {{
+      predict_regs(x, P, s_Q, dt);
+      {norm}
+    }}
+#pragma unroll
+    for (int i = 0; i < {D}; i++) rn::pin(x[i]);
+#pragma unroll
+    for (int i = 0; i < {EE}; i++) rn::pin(P[i]);
+    rn::async_wait();
+    rn::wave_lds_sync();
+    rn::lds_to_regs<{zmax}>(s_z, lane, z);
+    if (r_per_filter) rn::lds_to_regs<{ZZ}>(s_R, lane, Rf);
+    const bool live = lane < cnt && act != 0;
+    bool on = live;
+    int fl = 0, nf = 0;
+    if (live) {{
+      switch (kind) {{
+{nl.join(cases)}
+        default: on = false; break;      // not a kind of this model: untouched, flag 8
+      }}
+    }}
+    {norm}
+    rn::wave_lds_sync();
+    if (on) {{
+      rn::regs_to_lds<{D}>(s_x, lane, x);
+      rn::regs_to_lds<{EE}>(s_P, lane, P);
+      rn::regs_to_lds<{zmax}>(s_z, lane, z);
+    }}
+    rn::wave_lds_sync();
+    rn::tile_l2g<{D}>(gx + base * {D}, cnt, s_x, lane);
+    rn::tile_l2g<{EE}>(gP + base * {EE}, cnt, s_P, lane);
+    rn::tile_l2g<{zmax}>(gz + base * {zmax}, cnt, s_z, lane);
+    {{
+      double acc = 0.0;
+#pragma unroll
+      for (int i = 0; i < {D}; i++) acc += x[i];
+      if (!(acc - acc == 0.0)) nf = 2;          // non-finite state
+    }}
+    if (flags != nullptr && lane < cnt) flags[base + lane] = (uint8_t)(on ? (fl | nf) : (live ? 8 : 16));
+    rn::wave_lds_sync();
+  }}
+}}
+"""
+
+
+def launch_kinds(do_predict):
+  tf = "true" if do_predict else "false"
+  args = ("x, P, z, R, r_per_filter, kinds, Q, dt_vec, dt, n, norm_quats, flags, active" if do_predict else
+          "x, P, z, R, r_per_filter, kinds, nullptr, nullptr, 0.0, n, norm_quats, flags, active")
+  return f"""  const int64_t tiles = (n + 63) >> 6;
+  hipLaunchKernelGGL(k_kinds<{tf}>, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
+                     {args});"""
 
 
 def run_unroll(spec):

@@ -603,23 +603,26 @@ def kernels(spec):
     out.append("__device__ unsigned long long g_tl[256 * 64 * 2];      // debug timeline (tuning knob wide_timeline)")
     out.append("__device__ unsigned long long g_tlb[4096 * 2];         // start / end of EVERY workgroup's first tile")
 
-  def kernel(kname, k=None, ckpt=False):
+  def kernel(kname, k=None, ckpt=False, mixed=False):
+    # mixed: k_kinds, a kind per filter (kinds[i]) -- z rows at stride zmax, per-filter R at stride zmax^2 or a table in the order of the model's
+    # kinds; phase 1 and phase 3 switch per lane, phase 2 runs the matrix update of every kind a pass holds on the filters of that kind
     # ckpt: the kernel also writes a CHECKPOINT -- the observations as they came (cz), the filtered pair (cx, cP) --, what the orchestrators' rewind
     # rings keep of every call (ekf_sym.cc:142-156, 191); a kernel of its own (k_stepc_{kind}), k_step_{kind} stays as it is
-    upd = k is not None
-    Z = k.zdim if upd else 1
+    upd = k is not None or mixed
+    Z = (max(kk_.zdim for kk_ in spec.kinds) if mixed else k.zdim) if upd else 1
     ZZ = Z * Z
-    wide_s = upd and wide_z(k, spec.dim_err) and tune.wide_lean != 1 and k.He_sym is None
+    wide_s = upd and not mixed and wide_z(k, spec.dim_err) and tune.wide_lean != 1 and k.He_sym is None
     tmpl = "template <bool DO_PREDICT>\n" if upd else ""
     dop = "DO_PREDICT" if upd else "true"
-    sig_obs = ("double* __restrict__ gz, const double* __restrict__ gR, const int r_per_filter, const double* __restrict__ gea,\n    "
-               if upd else "")
+    sig_obs = ("double* __restrict__ gz, const double* __restrict__ gR, const int r_per_filter, " +
+               ("const int32_t* __restrict__ gkinds" if mixed else "const double* __restrict__ gea") + ",\n    " if upd else "")
     flags_arg = (", uint8_t* __restrict__ flags" if upd else "") + ", const uint8_t* __restrict__ active"
     if ckpt:
       flags_arg += ", double* __restrict__ cx, double* __restrict__ cP, double* __restrict__ cz"
     L = []
     A = L.append
-    TLK = tune.wide_timeline
+    TLK = tune.wide_timeline and not mixed
+    known = " || ".join(f"kd_ == {kk_.kind}" for kk_ in spec.kinds)
 
     def TL(idx):      # debug stamps (tuning knob wide_timeline): [block][slot][0] = shader cycles, [1] = 100 MHz wall clock
       if TLK:
@@ -640,6 +643,8 @@ def kernels(spec):
       if wide_s:
         A(f"  __shared__ __attribute__((aligned(16))) double s_S[{FPW} * {wide_s_doubles(k)}];      // the wide kind's innovation covariance, factored in place (_wide_obs_update)")
     A("  __shared__ __attribute__((aligned(16))) double s_sl[FT2 * SLOT];")
+    if mixed:
+      A("  __shared__ int s_kd[FT2];      // the kind each filter of the tile is updated with; 0: none (masked out, or not a kind of this model)")
     A("  const int lane = threadIdx.x;")
     A(f"  const int g = lane / {GL};")
     A(f"  const int c = lane % {GL};")
@@ -680,7 +685,14 @@ def kernels(spec):
     if ckpt:
       A(f"    rn::copy_l2g<FT2 * {Z}>(cz + base * {Z}, cnt * {Z}, s_z, lane);      // the observations, before the residuals take their place")
     TL(1)
-    A("    if (lane < cnt) {")
+    if mixed:
+      A("    int kd1 = 0;")
+      A("    if (lane < cnt) {")
+      A("      const int kd_ = gkinds[base + lane];")
+      A(f"      if ((active == nullptr || active[base + lane] != 0) && ({known})) kd1 = kd_;")
+      A("      s_kd[lane] = kd1;")
+      A("    }")
+    A("    if (lane < cnt" + (" && kd1 != 0" if mixed else "") + ") {")
     A("      double* sl = s_sl + lane * SLOT;")
     A("      if (do_pred) {")
     A("        int ld_ = lane;")
@@ -692,7 +704,14 @@ def kernels(spec):
     A("      }")
     if upd:
       A("      __builtin_amdgcn_sched_barrier(0);       // f / F first, then h / H: interleaved for ILP they need the sum of both register sets")
-      A(f"      {_obs_call(k, 'true')};")
+      if mixed:
+        A("      switch (kd1) {")
+        for kk_ in spec.kinds:
+          A(f"        case {kk_.kind}: scal_obs_{kk_.kind}(sl, s_z + lane * {Z}); break;")
+        A("        default: break;")
+        A("      }")
+      else:
+        A(f"      {_obs_call(k, 'true')};")
     A("    }")
     A("    rn::wave_lds_sync();")
     if tune.wide_lean == 1 and tune.wide_lean_q:
@@ -728,11 +747,19 @@ def kernels(spec):
     A("      const int gg = g < pcnt ? g : 0;")
     A("      // a masked-out filter (active[i] == 0) is not `on`: every LDS store of the matrix phase is predicated, so its image")
     A("      // of P goes back to HBM as it came")
-    A(f"      const bool on = act && g < pcnt && (active == nullptr || active[base + {FPW} * p + gg] != 0);")
+    if mixed:
+      A(f"      const int kd = (act && g < pcnt) ? s_kd[{FPW} * p + gg] : 0;")
+      A("      const bool on = kd != 0;")
+    else:
+      A(f"      const bool on = act && g < pcnt && (active == nullptr || active[base + {FPW} * p + gg] != 0);")
     A(f"      double* sl = s_sl + ({FPW} * p + gg) * SLOT;")
     A(f"      if (do_pred) mat_predict(sPc + gg * {EE}, qcol, sl, cc, on);")
     TL("5 + 4 * p")
-    if upd:
+    if mixed:
+      for ki_, kk_ in enumerate(spec.kinds):      # a kind no filter of the pass has is skipped (wave-uniform test)
+        A(f"      if (any_lane(kd == {kk_.kind}))")
+        A(f"        mat_update_{kk_.kind}(sPc + gg * {EE}, r_per_filter ? gR + (base + {FPW} * p + gg) * {ZZ} : gR + {ki_ * ZZ}, sl, sl, s_G + gg * {Z * E}, s_K + gg * {Z * E}, cc, kd == {kk_.kind});")
+    elif upd:
       ss_ = f", s_S + gg * {wide_s_doubles(k)}" if wide_s else ""
       A(f"      mat_update_{k.kind}(sPc + gg * {EE}, r_per_filter ? gR + (base + {FPW} * p + gg) * {ZZ} : gR, sl, sl, s_G + gg * {Z * E}, s_K + gg * {Z * E}{ss_}, cc, on);")
     TL("6 + 4 * p")
@@ -744,9 +771,20 @@ def kernels(spec):
     A("    }")
     TL(3)
     A("    // ---------------- phase 3: lane l = filter l, inject the error state, write x / y / flags ---------")
-    A("    if (lane < cnt && (active == nullptr || active[base + lane] != 0)) {")
+    if mixed:
+      A("    if (lane < cnt && kd1 != 0) {")
+    else:
+      A("    if (lane < cnt && (active == nullptr || active[base + lane] != 0)) {")
     A("      const double* sl = s_sl + lane * SLOT;")
-    if upd:
+    if mixed:
+      zcases = " ".join(f"case {kk_.kind}: zk_ = {kk_.zdim}; break;" for kk_ in spec.kinds)
+      A(f"      int fl = scal_inject(sl, s_x + lane * {D}, norm_quats);")
+      A("      int zk_ = 0;")
+      A(f"      switch (kd1) {{ {zcases} default: break; }}")
+      A("#pragma unroll")
+      A(f"      for (int i = 0; i < {Z}; i++) if (i < zk_) s_z[lane * {Z} + i] = sl[{lay.OFF_Y} + i];      // the rest of the row passes through")
+      A(f"      if (flags != nullptr) flags[base + lane] = (uint8_t)(fl | (int)sl[{lay.OFF_FL}]);     // 1 gated")
+    elif upd:
       A(f"      int fl = scal_inject(sl, s_x + lane * {D}, norm_quats);")
       A("#pragma unroll")
       A(f"      for (int i = 0; i < {Z}; i++) s_z[lane * {Z} + i] = sl[{lay.OFF_Y} + i];")
@@ -754,7 +792,10 @@ def kernels(spec):
     else:
       A("#pragma unroll")
       A(f"      for (int i = 0; i < {D}; i++) s_x[lane * {D} + i] = sl[{lay.OFF_X} + i];")
-    if upd:
+    if mixed:
+      A("    } else if (lane < cnt && flags != nullptr) {")
+      A("      flags[base + lane] = (active != nullptr && active[base + lane] == 0) ? 16 : 8;       // masked out / not a kind of this model: x, P and z pass through untouched")
+    elif upd:
       A("    } else if (lane < cnt && flags != nullptr) {")
       A("      flags[base + lane] = 16;       // masked out: x, P and z pass through untouched")
     A("    }")
@@ -776,6 +817,18 @@ def kernels(spec):
   for k in spec.kinds:
     out.append(kernel(f"k_step_{k.kind}", k))
     out.append(kernel(f"k_stepc_{k.kind}", k, ckpt=True))
+  from rednose_amd.codegen import emit as _emit
+  if _emit.step_kinds(spec):
+    out.append("""
+// Does any lane of the wavefront hold `p`?  (k_kinds skips the matrix update of a kind no filter of a pass has: an optimisation only, every
+// store of the matrix phase is predicated.  A host build of this text, the kernels running lane by lane as threads, takes every update.)
+#ifdef __HIP__
+__device__ __forceinline__ bool any_lane(const bool p) { return __ballot(p) != 0ull; }
+#else
+inline bool any_lane(bool) { return true; }
+#endif
+""")
+    out.append(kernel("k_kinds", mixed=True))
   return "\n".join(out)
 
 
@@ -887,3 +940,12 @@ def launch_step_ckpt(kind):
   return f"""  const int64_t tiles = (n + FT2 - 1) / FT2;
   hipLaunchKernelGGL(k_stepc_{kind}<true>, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
                      x, P, z, R, r_per_filter, ea, Q, dt_vec, dt, n, norm_quats, flags, active, ckpt_x, ckpt_P, ckpt_z);"""
+
+
+def launch_kinds(do_predict):
+  tf = "true" if do_predict else "false"
+  args = ("x, P, z, R, r_per_filter, kinds, Q, dt_vec, dt, n, norm_quats, flags, active" if do_predict else
+          "x, P, z, R, r_per_filter, kinds, nullptr, nullptr, 0.0, n, norm_quats, flags, active")
+  return f"""  const int64_t tiles = (n + FT2 - 1) / FT2;
+  hipLaunchKernelGGL(k_kinds<{tf}>, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
+                     {args});"""

@@ -100,6 +100,10 @@ def gen_code(folder, name, f_sym, dt_sym, x_sym, obs_eqs, dim_x, dim_err, eskf_p
         warnings.warn(f"{name}: smoother kernel {rts_scratch()} does not fit the register file (see {folder}/{name}.kernels.txt); "
                       f"lib{name}.so is built WITHOUT batch_rts", RuntimeWarning)
         usage, bad = fall_back("no_rts", "the smoother still touches scratch memory: library without batch_rts")
+      kinds_bad = [k for k, u in usage.items() if k.startswith("k_kinds") and (u["scratch"] > 0 or u["vgpr_spill"] > 0)]
+      if kinds_bad:
+        # the per-kind step kernels are intact: a call that mixes kinds is then one `_masked` launch per kind ({name}_has_step_kinds() == 0)
+        usage, bad = fall_back("no_kinds", f"the mixed-kind step kernel {kinds_bad} does not fit the register file: library without it")
     with open(stamp_fn, "w", encoding="utf-8") as f:
       f.write(digest)
   return spec
@@ -924,6 +928,140 @@ class BatchedEKF:
     if keep_estimate:
       return est[0], xk_k, est[1], Pk_k, tt, kind, zl[0], z_obs[0], extra_args
     return zl[0]
+
+  # -- a kind per filter in one call ---------------------------------------------------------------------------------
+  def _has_step_kinds(self):
+    fn = getattr(self._lib, f"{self.name}_has_step_kinds", None)
+    return fn is not None and int(fn()) == 1
+
+  def predict_and_update_kinds(self, t, kinds, z, R, active=None):
+    """One call on per-filter timelines in which every filter brings its OWN observation kind (what N independent EKFSym instances do at a tick:
+    `updates.at(kind)`, ekf_sym.cc:196-219).  kinds: (N,) ints, an entry <= 0 = no observation for that filter in this call; z: (N, zmax), the
+    first Z of a row are that filter's observation (consumed: overwritten by the residual, the rest of the row passes through); R: a dict
+    {kind: (Z, Z)} shared by the filters of a kind, or (N, zmax, zmax) per filter (leading Z x Z block); t / active as predict_and_update_batch.
+    Returns the (N, zmax) residuals.
+
+    In order, with the library's mixed-kind kernel: batch_timeline_plan -> one integer read back -> batch_predict_update_kinds (ONE launch,
+    the state crosses HBM once whatever the mix) -> batch_timeline_push_kinds; the ring entries are those the per-kind calls write.  With a late
+    filter in the call, or a library without the kernel ({name}_has_step_kinds() == 0): one predict_and_update_batch(active = kinds == k) per
+    kind present, late observations rewinding as ever."""
+    torch = self._torch
+    N, zmax = self.batch, max(self.zdims.values())
+    if not self.per_filter:
+      if len(self.rewind_t) > 0 and self.rewind_to_keep > 0:
+        raise KalmanError("this orchestrator already holds shared-timeline checkpoints: construct it with per_filter=True")
+      self.per_filter = True
+    if not self._device_timeline:
+      raise KalmanError("predict_and_update_kinds needs the device timeline (device_timeline=True and a library with batch_timeline_plan / _push)")
+    if isinstance(kinds, torch.Tensor) and kinds.is_cuda:
+      # kinds that live on the device already: which are present is one more read back (a sort + a wait) in front of the plan -- hand in
+      # a numpy array or a list to keep the call at one integer
+      kd = kinds.to(device=self.device, dtype=torch.int32).expand(N).contiguous()
+      present = [int(k) for k in torch.unique(kd).tolist() if int(k) > 0]
+    else:
+      kh = np.broadcast_to(np.asarray(kinds.numpy() if isinstance(kinds, torch.Tensor) else kinds).astype(np.int32), (N,))
+      present = [int(k) for k in np.unique(kh) if int(k) > 0]       # (on the host, before the upload: the kinds decide what is launched)
+      kd = torch.as_tensor(np.ascontiguousarray(kh)).to(self.device)
+    for k in present:
+      if k not in self.zdims:
+        raise KeyError(k)
+    zt = z if isinstance(z, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(z, dtype=np.float64))
+    zt = zt.to(device=self.device, dtype=torch.float64)
+    if tuple(zt.shape) != (N, zmax):
+      raise KalmanError(f"predict_and_update_kinds: z must be (N, zmax) = ({N}, {zmax}), got {tuple(zt.shape)}")
+    zt = zt.contiguous()
+    if isinstance(R, dict):
+      key = ("kinds",) + tuple((k, np.asarray(R[k], dtype=np.float64).tobytes()) for k in sorted(R))
+      Rd = self._R_cache.get(key)
+      if Rd is None:
+        tab = np.zeros((len(self.kinds), zmax * zmax))
+        for i, k in enumerate(self.kinds):
+          if k in R:
+            Z = self.zdims[k]
+            tab[i, :Z * Z] = np.asarray(R[k], dtype=np.float64).reshape(Z * Z)
+        Rd = self._R_cache[key] = self._dev(tab)
+        while len(self._R_cache) > self.R_CACHE_ENTRIES:
+          self._R_cache.popitem(last=False)
+      for k in present:
+        if k not in R:
+          raise KeyError(k)
+      per = 0
+    else:
+      Rfull = self._dev(R, (N, zmax, zmax))
+      Zf = torch.zeros(N, dtype=torch.int64, device=self.device)
+      for k in present:
+        Zf[kd == k] = self.zdims[k]
+      # leading Z x Z block of every filter, compact and row-major in front of its row (the convention of batch_run)
+      Rd = torch.zeros((N, zmax * zmax), dtype=torch.float64, device=self.device)
+      for k in present:
+        Z, m = self.zdims[k], kd == k
+        Rd[m, :Z * Z] = Rfull[m][:, :Z, :Z].reshape(-1, Z * Z)
+      per = 1
+    has = kd > 0
+    if active is not None:
+      has = has & torch.as_tensor(active, device=self.device).to(torch.bool).expand(N)
+    if self._has_step_kinds():
+      ret = self._timeline_call_kinds(t, has, kd, zt, Rd, per)
+      if ret is not None:
+        self.pf_stats["fast"] += 1
+        return ret
+      t = self._keepalive_timeline[0]
+    # the per-kind path: a filter is late, or the library has no mixed-kind kernel
+    self.pf_stats["legacy"] += 1
+    fl = torch.full((N,), 16, dtype=torch.uint8, device=self.device)
+    stats = dict(self.pf_stats)
+    for k in present:
+      Z, m = self.zdims[k], has & (kd == k)
+      zk = zt[:, :Z].contiguous()
+      Rk = (Rd[self.kinds.index(k), :Z * Z].reshape(Z, Z) if not per else Rd[:, :Z * Z].reshape(N, Z, Z).contiguous())
+      if per:
+        Rk = torch.where(m[:, None, None], Rk, torch.eye(Z, dtype=torch.float64, device=self.device))      # (filters of other kinds: any regular matrix)
+      y = self.predict_and_update_batch(t, k, zk, Rk, active=m)
+      zt[:, :Z] = torch.where(m[:, None], y, zt[:, :Z])
+      fl = torch.where(m, self.flags, fl)
+    self.pf_stats = stats
+    self.flags.copy_(fl)
+    return zt
+
+  def _timeline_call_kinds(self, t, has, kd, zt, Rd, per):
+    """_timeline_call for a kind per filter: plan, the count of late filters read back, ONE mixed-kind step, the checkpoint.  None (nothing
+    modified) when a filter is late."""
+    torch = self._torch
+    N, K, zmax = self.batch, max(self.rewind_to_keep, 0), max(self.zdims.values())
+    if isinstance(t, torch.Tensor) and t.device == self.device and t.dtype == torch.float64 and tuple(t.shape) == (N,) and t.is_contiguous():
+      tt = t
+    else:
+      tt = torch.full((N,), float(t), dtype=torch.float64, device=self.device) if np.isscalar(t) else self._dev(t, (N,))
+    a8 = has.view(torch.uint8).contiguous()
+    ft = self.filter_time
+    if ft is None or ft is not self._ft_dev:
+      ft = self.filter_times()
+      ft = ft.contiguous().clone() if ft is self.filter_time else ft
+      self._ft_dev = self.filter_time = ft
+    copy_z = K > 0
+    b = self._timeline_buffers(N * zmax if copy_z else 0)
+    self._call("batch_timeline_plan", self._p(tt), self._p(a8), self._p(ft), N, self._p(b["dt"]), self._p(b["act"]), self._p(b["late"]),
+               self._p(b["n_late"]), self._p(zt) if copy_z else None, self._p(b["z_keep"]) if copy_z else None, N * zmax if copy_z else 0, self._stream())
+    b["host"].copy_(b["n_late"], non_blocking=True)
+    torch.cuda.current_stream(self.device).synchronize()
+    count = int(b["host_np"][0])
+    late, b["seen"] = count != b["seen"], count
+    self._keepalive_timeline = (tt, a8, kd, zt, Rd)
+    if late:
+      return None
+    self._call("batch_predict_update_kinds", self._p(self.x), self._p(self.P), self._p(self.Q), self._p(b["dt"]), 0.0, self._p(kd), self._p(zt), self._p(Rd), per,
+               N, self.norm_quats, self._p(self.flags), self._p(b["act"]), self._stream())
+    if K > 0:
+      if self._ring is None:
+        self._ring_alloc(1)
+      r = self._ring
+      self._call("batch_timeline_push_kinds", self._p(tt), self._p(b["act"]), self._p(ft), self._p(self.x), self._p(self.P), N, K, r["nmax"],
+                 self._p(r["t"]), self._p(r["x"]), self._p(r["P"]), self._p(r["kind"]), self._p(r["nobs"]), self._p(r["z"]), self._p(r["R"]), self._p(r["ea"]),
+                 self._p(r["head"]), self._p(r["length"]), self._p(kd), self._p(b["z_keep"]), self._p(Rd), per, self._stream())
+    else:
+      self._call("batch_timeline_push_kinds", self._p(tt), self._p(b["act"]), self._p(ft), None, None, N, 0, 0, None, None, None, None, None, None, None, None,
+                 None, None, self._p(kd), None, None, 0, self._stream())
+    return zt
 
   # -- the in-order call with its bookkeeping on the device ----------------------------------------------------------
   # The checkpoint wants the observation as it came and the step overwrites it: True = k_timeline_plan copies it aside (no launch of its

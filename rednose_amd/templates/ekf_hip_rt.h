@@ -857,6 +857,15 @@ struct TimelineObs {
   int64_t z_sf, z_so, r_sf, r_so, ea_sf, ea_so;
 };
 
+// A kind per filter (batch_timeline_push_kinds): kinds[f] is filter f's kind, with its Z looked up in the model's table; one observation per
+// filter, rows of z at stride zmax, R per filter at stride zmax^2 (compact Z x Z in front) or -- r_sf == 0 -- row `index of the kind` of a table
+// of such rows.  kinds == NULL: the call's one kind and count (batch_timeline_push).
+struct TimelineKinds {
+  const int32_t* kinds;
+  int count;
+  struct { int32_t kind, Z; } tab[16];
+};
+
 // The whole checkpoint of a call in one launch, for the filters with act[f] != 0: ft[f] = t[f], the filter's ring advances by one entry
 // (overwriting its oldest when full) and the entry takes t, x, P, kind, nobs and the call's nobs observations with their noise and
 // extra arguments (EKFSym::checkpoint, ekf_sym.cc:142-156, for n filter instances at once).  One
@@ -864,10 +873,20 @@ struct TimelineObs {
 __global__ __launch_bounds__(256) void k_timeline_push(const double* __restrict__ t, const uint8_t* __restrict__ act, double* __restrict__ ft,
                                                        const double* __restrict__ x, const double* __restrict__ P, const int64_t n, const int D,
                                                        const int EE, const TimelineRing r, const int kind, const int nobs, const int Z,
-                                                       const int EA, const int zmax, const int eamax, const TimelineObs o) {
+                                                       const int EA, const int zmax, const int eamax, const TimelineObs o, const TimelineKinds tk) {
   const int lane = threadIdx.x & (WAVE - 1);
   for (int64_t f = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); f < n; f += (int64_t)gridDim.x * 4) {
     if (act[f] == 0) continue;
+    int kind_f = kind, Zf = Z;
+    int64_t r_tab = 0;                 // a table of R rows: where this filter's kind has its row
+    if (tk.kinds != nullptr) {         // a kind per filter
+      kind_f = tk.kinds[f];
+      int ki = -1;
+      for (int i = 0; i < tk.count; i++) if (tk.tab[i].kind == kind_f) ki = i;
+      if (ki < 0) continue;            // not a kind of this model: the step left the filter alone, so does the checkpoint
+      Zf = tk.tab[ki].Z;
+      if (o.r_sf == 0) r_tab = (int64_t)ki * zmax * zmax;
+    }
     const double tf = t[f];
     if (r.K <= 0) {
       if (lane == 0) ft[f] = tf;
@@ -888,7 +907,7 @@ __global__ __launch_bounds__(256) void k_timeline_push(const double* __restrict_
       r.head[f] = head;
       r.length[f] = length;
       r.t[e] = tf;
-      r.kind[e] = kind;
+      r.kind[e] = kind_f;
       r.nobs[e] = nobs;
     }
     wave_copy(r.x + e * D, x + f * D, D, lane);
@@ -896,13 +915,13 @@ __global__ __launch_bounds__(256) void k_timeline_push(const double* __restrict_
     double* rz = r.z + e * r.nmax * zmax;
     double* rR = r.R + e * r.nmax * zmax * zmax;
     double* rea = r.ea + e * r.nmax * eamax;
-    for (int i = lane; i < nobs * Z; i += WAVE) {
-      const int j = i / Z, c = i - j * Z;
+    for (int i = lane; i < nobs * Zf; i += WAVE) {
+      const int j = i / Zf, c = i - j * Zf;
       rz[j * zmax + c] = o.z[f * o.z_sf + j * o.z_so + c];
     }
-    for (int i = lane; i < nobs * Z * Z; i += WAVE) {
-      const int j = i / (Z * Z), q = i - j * (Z * Z), row = q / Z, c = q - row * Z;
-      rR[(j * zmax + row) * zmax + c] = o.R[f * o.r_sf + j * o.r_so + q];
+    for (int i = lane; i < nobs * Zf * Zf; i += WAVE) {
+      const int j = i / (Zf * Zf), q = i - j * (Zf * Zf), row = q / Zf, c = q - row * Zf;
+      rR[(j * zmax + row) * zmax + c] = o.R[r_tab + f * o.r_sf + j * o.r_so + q];
     }
     for (int i = lane; i < nobs * EA; i += WAVE) {
       const int j = i / EA, c = i - j * EA;
