@@ -1,5 +1,5 @@
-"""Pieces shared by the kernel emitters: structured (sparse-at-generation-time) matrices and
-the per-routine device functions / host wrappers of the reference's scalar C ABI."""
+"""Pieces shared by the kernel emitters: structured (sparse-at-generation-time) matrices, the per-routine device
+functions of the reference's scalar C ABI, and the launch text of the step-granular kernels (launch_*)."""
 import sympy as sp
 
 from rednose_amd.codegen.lower import Block, vector_names
@@ -56,6 +56,11 @@ class SMat:
 
   def col_nz(self, j):
     return [(i, self.e[i][j]) for i in range(self.rows) if self.e[i][j] is not None]
+
+
+def ea_count(k):
+  """Number of extra arguments of kind k (0: the `ea` pointer is ignored)."""
+  return 0 if k.ea_sym is None else int(sp.Matrix(k.ea_sym).shape[0])
 
 
 def term(coef, operand):
@@ -136,3 +141,34 @@ def innovation_solver(Z, general, y_terms, thresh=None):
     gate += [f"  if (d2 > {thresh!r}) {{", "    gated = 1;", "#pragma unroll",
              f"    for (int i = 0; i < {Z * Z}; i++) {{ Rl[i] = 1.0e16 * Rl[i]; S[i] = HPH[i] + Rl[i]; }}", f"    {factor}", "  }", "}"]
   return factor, gate, (lambda v: f"{pre}_solve<{Z}>(L, iL, {v});")
+
+
+# ---- launch text of the step-granular kernels, the same in both kernel families but for `tiles`, the family's count of wavefront tiles in n ----
+def _launch(tiles, kernel, args):
+  return f"""  const int64_t tiles = {tiles};
+  hipLaunchKernelGGL({kernel}, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
+                     {args});"""
+
+
+def launch_predict(tiles):
+  return _launch(tiles, "k_predict", "x, P, Q, dt_vec, dt, n, norm_quats, active")
+
+
+def _step_args(obs, do_predict):
+  return f"x, P, z, R, r_per_filter, {obs}, {'Q, dt_vec, dt' if do_predict else 'nullptr, nullptr, 0.0'}, n, norm_quats, flags, active"
+
+
+def launch_step(tiles, kind, do_predict):
+  return _launch(tiles, f"k_step_{kind}<{'true' if do_predict else 'false'}>", _step_args("ea", do_predict))
+
+
+def launch_step_ckpt(tiles, kind):
+  return _launch(tiles, f"k_stepc_{kind}<true>", _step_args("ea", True) + ", ckpt_x, ckpt_P, ckpt_z")
+
+
+def launch_kinds(tiles, do_predict):
+  return _launch(tiles, f"k_kinds<{'true' if do_predict else 'false'}>", _step_args("kinds", do_predict))
+
+
+def launch_maha(tiles, kind, ea=True):
+  return _launch(tiles, f"k_maha_{kind}", f"x, P, z, R, r_per_filter, {'ea, ' if ea else ''}n, d2")

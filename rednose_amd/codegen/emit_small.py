@@ -20,12 +20,23 @@ Algebra emitted (reference lines in /root/reference/rednose/templates/ekf_c.c):
                      P' = B + (K R - C) K^T (= B I_KH^T + K R K^T)
                   which is the same polynomial in the same inputs -- including the property that the
                   rounding error of B is cancelled to first order by the correction term.
+
+Where things are: predict_regs / update_regs / maha_regs print the algebra on registers.  kernels() strings the library's kernels together: k_predict,
+then step_kernel() for k_step_{kind}, k_stepc_{kind} (+ checkpoint) and -- through kinds_kernel() -- k_kinds (a kind per filter); it is made of
+named pieces (LDS images, TILE_LOOP, the tile requests with z last and a counted wait or all behind one wait, predict + pins, the split and the
+unsplit write-back, the non-finite test, the timeline stamps) of which k_predict, k_maha_{kind} and k_run take those that apply.  kind_cases()
+is the per-kind `switch` of k_kinds, k_run, k_run_blk and k_run_blk_tr.  The launch text of the step-granular kernels is emit_common's, bound to
+this family's TILES; launch_run is this family's own.
 """
+import functools
+
 import sympy as sp
 
-from rednose_amd.codegen import tuning
+from rednose_amd.codegen import emit_common, tuning
 from rednose_amd.codegen.lower import Block, vector_names
-from rednose_amd.codegen.emit_common import SMat, term, sum_terms, innovation_solver
+from rednose_amd.codegen.emit_common import SMat, term, sum_terms, innovation_solver, ea_count
+
+TILES = "(n + 63) >> 6"      # tiles of a launch: 64 filters per wavefront
 
 
 def _ind(lines, n=2):
@@ -246,15 +257,9 @@ def maha_kernels(spec):
 __global__ __launch_bounds__(64) void k_maha_{k.kind}(const double* __restrict__ gx, const double* __restrict__ gP,
     const double* __restrict__ gz, const double* __restrict__ gR, const int r_per_filter, const int64_t n,
     double* __restrict__ d2) {{
-  __shared__ __attribute__((aligned(16))) double s_x[64 * {D | 1}];
-  __shared__ __attribute__((aligned(16))) double s_P[64 * {EE | 1}];
-  __shared__ __attribute__((aligned(16))) double s_z[64 * {Z | 1}];
-  __shared__ __attribute__((aligned(16))) double s_R[64 * {ZZ | 1}];
+{_lds(x=D, P=EE, z=Z, R=ZZ)}
   const int lane = threadIdx.x;
-  const int64_t tiles = (n + 63) >> 6;
-  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {{
-    const int64_t base = tile << 6;
-    const int cnt = (n - base) < 64 ? (int)(n - base) : 64;
+{TILE_LOOP}
     rn::tile_g2l_async<{D}>(gx + base * {D}, cnt, s_x, lane);
     rn::tile_g2l_async<{EE}>(gP + base * {EE}, cnt, s_P, lane);
     rn::tile_g2l_async<{Z}>(gz + base * {Z}, cnt, s_z, lane);
@@ -280,22 +285,84 @@ __global__ __launch_bounds__(64) void k_maha_{k.kind}(const double* __restrict__
   return "\n".join(out)
 
 
-def launch_maha(kind):
-  return f"""  const int64_t tiles = (n + 63) >> 6;
-  hipLaunchKernelGGL(k_maha_{kind}, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
-                     x, P, z, R, r_per_filter, n, d2);"""
-
-
 def norm_text(spec):
   """Quaternion renormalisation after predict / update (EKFSym::normalize_quaternions, ekf_sym.cc:69-77,207,213)."""
   quat = "".join(f" rn::normalize_quat<{spec.dim_x}>(x, {q});" for q in spec.quaternion_idxs)
   return f"if (norm_quats) {{{quat} }}" if spec.quaternion_idxs else "(void)norm_quats;"
 
 
+# ---- pieces of the kernels' text: a tile of 64 filters between HBM, the wavefront's LDS slice and the lanes' registers -------------------------
+TILE_LOOP = """  const int64_t tiles = (n + 63) >> 6;
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int64_t base = tile << 6;
+    const int cnt = (n - base) < 64 ? (int)(n - base) : 64;"""
+
+
+def _lds(flat=False, **doubles):
+  """LDS declarations.  s_{name}: the image of a tile, `doubles` per filter in rows padded to an odd count; flat: an array of that many doubles."""
+  return "\n".join(f"  __shared__ __attribute__((aligned(16))) double s_{a}[{n if flat else f'64 * {n | 1}'}];" for a, n in doubles.items())
+
+
+def _tile_in(n, g, s):
+  return f"rn::tile_g2l_async<{n}>({g} + base * {n}, cnt, {s}, lane);"
+
+
+def _tile_out(n, g, s):
+  return f"rn::tile_l2g<{n}>({g} + base * {n}, cnt, {s}, lane);"
+
+
+def _pin(n, reg):
+  return f"#pragma unroll\n    for (int i = 0; i < {n}; i++) rn::pin({reg}[i]);"
+
+
+def _flag_acc(D):
+  """The non-finite test on the state: a sum that is not finite fails acc - acc == 0."""
+  return f"""double acc = 0.0;
+#pragma unroll
+      for (int i = 0; i < {D}; i++) acc += x[i];
+      if (!(acc - acc == 0.0)) nf = 2;          // non-finite state"""
+
+
+def kind_cases(spec, suffix, z, R, R_shared=None, extra="", ea_lane=None, ind=8):
+  """The `case {kind}: { .. }` blocks of a switch over the model's kinds.  The observation and its covariance are copied into arrays of the kind's
+  own size -- zk from `z`[i], Rk from the expression `R` in i (R_shared(idx): the expression for `!r_per_filter`, idx the kind's position in the
+  model) --, fl = update_{kind}{suffix}(x, P, zk, Rk ..) runs, the residual goes back to `z`.  `extra`: text behind the call's arguments.  `ea_lane`:
+  the lane's filter within the tile in the (T, n, EA) array of per-step extra arguments; a kind that takes them sets flag 8 without the array."""
+  pad = " " * ind
+  EAM = max(ea_count(k) for k in spec.kinds)
+  cases = []
+  for idx, k in enumerate(spec.kinds):
+    Z = k.zdim
+    ea, guard = "", ""
+    if k.ea_sym is not None and ea_lane is not None:
+      ea = f", gea + ((int64_t)t * n + base + {ea_lane}) * {EAM}"
+      guard = f"{pad}  if (gea == nullptr) {{ fl = 8; break; }}\n"
+    copy_R = f"#pragma unroll\n{pad}  for (int i = 0; i < {Z * Z}; i++) Rk[i] = {R};"
+    if R_shared is not None:
+      copy_R = f"""{pad}  if (r_per_filter) {{
+#pragma unroll
+{pad}    for (int i = 0; i < {Z * Z}; i++) Rk[i] = {R};
+{pad}  }} else {{
+#pragma unroll
+{pad}    for (int i = 0; i < {Z * Z}; i++) Rk[i] = {R_shared(idx)};
+{pad}  }}"""
+    cases.append(f"""{pad}case {k.kind}: {{
+{guard}{pad}  double zk[{Z}], Rk[{Z * Z}];
+#pragma unroll
+{pad}  for (int i = 0; i < {Z}; i++) zk[i] = {z}[i];
+{copy_R}
+{pad}  fl = update_{k.kind}{suffix}(x, P, zk, Rk{ea}{extra});
+#pragma unroll
+{pad}  for (int i = 0; i < {Z}; i++) {z}[i] = zk[i];
+{pad}  break;
+{pad}}}""")
+  return "\n".join(cases)
+
+
 def kernels(spec):
   """Device functions + __global__ kernels of family S for every kind."""
   tune = tuning.current()
-  waves, zwait, split, tline = tune.small_waves, tune.small_zwait, bool(tune.small_split), bool(tune.small_timeline)
+  waves, split = tune.small_waves, bool(tune.small_split)
   kattr = f" __attribute__((amdgpu_waves_per_eu({waves}, {waves})))" if waves else ""
   D, E = spec.dim_x, spec.dim_err
   EE = E * E
@@ -330,7 +397,7 @@ inline double lane_dt(const double* lds, int lane) { return lds[lane]; }
 #endif
 """)
   norm = norm_text(spec)
-  if tline:
+  if tune.small_timeline:
     out.append("__device__ unsigned long long g_tl[256 * 8 * 2];      // debug timeline (tuning knob small_timeline)")
 
   out.append(f"""
@@ -338,17 +405,13 @@ inline double lane_dt(const double* lds, int lane) { return lds[lane]; }
 __global__ __launch_bounds__(64) void k_predict(double* __restrict__ gx, double* __restrict__ gP,
     const double* __restrict__ gQ, const double* __restrict__ gdt, const double dt_scalar, const int64_t n,
     const int norm_quats, const uint8_t* __restrict__ active) {{
-  __shared__ __attribute__((aligned(16))) double s_x[64 * {D | 1}];
-  __shared__ __attribute__((aligned(16))) double s_P[64 * {EE | 1}];
-  __shared__ __attribute__((aligned(16))) double s_Q[{EE}];
+{_lds(x=D, P=EE)}
+{_lds(True, Q=EE)}
   const int lane = threadIdx.x;
   for (int i = lane; i < {EE}; i += 64) s_Q[i] = gQ[i];       // Q as LDS broadcast operands (36 SGPR pairs spilled otherwise)
-  const int64_t tiles = (n + 63) >> 6;
-  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {{
-    const int64_t base = tile << 6;
-    const int cnt = (n - base) < 64 ? (int)(n - base) : 64;
-    rn::tile_g2l_async<{D}>(gx + base * {D}, cnt, s_x, lane);
-    rn::tile_g2l_async<{EE}>(gP + base * {EE}, cnt, s_P, lane);
+{TILE_LOOP}
+    {_tile_in(D, "gx", "s_x")}
+    {_tile_in(EE, "gP", "s_P")}
     const double dt = (gdt != nullptr && lane < cnt) ? gdt[base + lane] : dt_scalar;
     rn::async_wait();
     rn::wave_lds_sync();
@@ -365,176 +428,18 @@ __global__ __launch_bounds__(64) void k_predict(double* __restrict__ gx, double*
       rn::regs_to_lds<{EE}>(s_P, lane, P);
     }}
     rn::wave_lds_sync();
-    rn::tile_l2g<{D}>(gx + base * {D}, cnt, s_x, lane);
-    rn::tile_l2g<{EE}>(gP + base * {EE}, cnt, s_P, lane);
+    {_tile_out(D, "gx", "s_x")}
+    {_tile_out(EE, "gP", "s_P")}
     rn::wave_lds_sync();
   }}
 }}
 """)
-  for k in spec.kinds:
-    Z = k.zdim
-    ZZ = Z * Z
-    # extra arguments are per observation, i.e. per filter of the batch: (n, len(ea)) row-major
-    ea = f", gea + (base + (lane < cnt ? lane : 0)) * {int(sp.Matrix(k.ea_sym).shape[0])}" if k.ea_sym is not None else ""
-    # k_stepc_{kind}: the same kernel writing a CHECKPOINT on its way -- the observations as they came (cz) and the filtered pair (cx, cP): what the
-    # orchestrators' rewind rings keep of every call (ekf_sym.cc:142-156, 191).  A kernel of its own, so that k_step_{kind} stays as it is.
-    for ckpt in (False, True):
-      kn = f"k_stepc_{k.kind}" if ckpt else f"k_step_{k.kind}"
-      cargs = ", double* __restrict__ cx, double* __restrict__ cP, double* __restrict__ cz" if ckpt else ""
-      cz_store = f"\n    rn::tile_l2g<{Z}>(cz + base * {Z}, cnt, s_z, lane);      // the observations, before the residuals take their place" if ckpt else ""
-      cx_store = f"\n    rn::tile_l2g<{D}>(cx + base * {D}, cnt, s_x, lane);" if ckpt else ""
-      cP_store = f"\n    rn::tile_l2g<{EE}>(cP + base * {EE}, cnt, s_P, lane);" if ckpt else ""
-
-      tl_pin = f"""
-#pragma unroll
-    for (int i = 0; i < {EE}; i++) rn::pin(P[i]);""" if tline else ""      # stamped builds: a phase's arithmetic ends at its stamp
-
-      def TL(i):      # debug stamps (tuning knob small_timeline; tools/timeline.py small): shader cycles and the 100 MHz wall clock, in scalar registers
-        return f"\n    if (tl_on) {{ tl_c[{i}] = __builtin_readcyclecounter(); tl_w[{i}] = wall_clock64(); }}" if tline else ""
-      act = """
-    // masked-out filters (active[i] == 0) pass through untouched: x, P and z leave as they came, flag bit 4 is set.  The mask is requested
-    // behind the tiles: hipcc turns it into a lane mask at once, i.e. waits for it and for everything in front of it -- one round trip for all
-    uint8_t act = 1;
-    if (active != nullptr) act = active[base + (lane < cnt ? lane : cnt - 1)];"""
-      tile_x = f"rn::tile_g2l_async<{D}>(gx + base * {D}, cnt, s_x, lane);"
-      tile_P = f"rn::tile_g2l_async<{EE}>(gP + base * {EE}, cnt, s_P, lane);"
-      tile_z = f"rn::tile_g2l_async<{Z}>(gz + base * {Z}, cnt, s_z, lane);"
-      tile_R = f"if (r_per_filter) rn::tile_g2l_async<{ZZ}>(gR + base * {ZZ}, cnt, s_R, lane);"
-      # the per-filter dt rides with the tiles (LDS-DMA, clamped inside a ragged tile: a lane without a filter stores nothing)
-      tile_dt = "if (DO_PREDICT && gdt != nullptr) lane_dt_request(gdt + base + (lane < cnt ? lane : cnt - 1), s_dt, lane);"
-      read_dt = "const double dt = (DO_PREDICT && gdt != nullptr) ? lane_dt(s_dt, lane) : dt_scalar;"
-      read_xP = f"""rn::lds_to_regs<{D}>(s_x, lane, x);
-    rn::lds_to_regs<{EE}>(s_P, lane, P);"""
-      read_zR = f"""rn::lds_to_regs<{Z}>(s_z, lane, z);
-    if (r_per_filter) rn::lds_to_regs<{ZZ}>(s_R, lane, R);"""
-      predict = f"""if (DO_PREDICT) {{
-      predict_regs(x, P, s_Q, dt);
-      {norm}
-    }}"""
-      if zwait == 1:
-        # vmcnt retires in issue order, so the tile that may stay in flight goes last: the observations are first read by the update, after
-        # 42 LDS reads and the whole predict; in a stream they are also the slowest tile (a buffer nothing has touched since it was written: HBM,
-        # while x and P were written by the previous launch and sit in the L2 / Infinity Cache)
-        load = f"""{tile_x}
-    {tile_P}
-    {tile_R}
-    {tile_dt}
-    {tile_z}{TL(1)}{act}
-    wait_but_tile<{Z}>(cnt);
-    rn::wave_lds_sync();{TL(2)}
-    double x[{D}], P[{EE}], z[{Z}];
-    {read_dt}
-    {read_xP}
-    {predict}
-    // (the predict's arithmetic ends here: without the pins hipcc sinks it below the wait, into the update's)
-#pragma unroll
-    for (int i = 0; i < {D}; i++) rn::pin(x[i]);
-#pragma unroll
-    for (int i = 0; i < {EE}; i++) rn::pin(P[i]);{TL(4)}
-    rn::async_wait();
-    rn::wave_lds_sync();{TL(3)}{cz_store}
-    {read_zR}"""
-      else:
-        # one wait for all tiles; 0: the observations first (they are the slowest tile, see above), 2: between x and P
-        order = [tile_z, tile_R, tile_x, tile_P] if zwait == 0 else [tile_x, tile_R, tile_z, tile_P]
-        nl = "\n    "
-        tlw = (f"\n    if (tl_on && cnt == 64) rn::async_wait_but<{(32 * D + 63) // 64 + (32 * EE + 63) // 64}>();{TL(3)}" if (tline and zwait == 0) else
-               (f"\n    if (tl_on && cnt == 64) rn::async_wait_but<{(32 * EE + 63) // 64}>();{TL(3)}" if tline else ""))
-        load = f"""{nl.join(order)}
-    {tile_dt}{TL(1)}{act}{tlw}
-    rn::async_wait();
-    rn::wave_lds_sync();{TL(2)}{cz_store}
-    double x[{D}], P[{EE}], z[{Z}];
-    {read_dt}
-    {read_xP}
-    {read_zR}
-    {predict}{tl_pin}{TL(4)}"""
-      flag_acc = f"""double acc = 0.0;
-#pragma unroll
-      for (int i = 0; i < {D}; i++) acc += x[i];
-      if (!(acc - acc == 0.0)) nf = 2;          // non-finite state"""
-      if split:
-        # x and the residual are final before the Joseph form, the bulk of the update's arithmetic: they leave there, P follows alone
-        update = f"""int nf = 0;
-    int fl = update_{k.kind}_regs_split(x, P, z, R{ea}, [&]() {{
-      {norm}
-      rn::wave_lds_sync();
-      if (on) {{
-        rn::regs_to_lds<{D}>(s_x, lane, x);
-        rn::regs_to_lds<{Z}>(s_z, lane, z);
-      }}
-      rn::wave_lds_sync();
-      rn::tile_l2g<{D}>(gx + base * {D}, cnt, s_x, lane);
-      rn::tile_l2g<{Z}>(gz + base * {Z}, cnt, s_z, lane);{cx_store.replace(chr(10) + "    ", chr(10) + "      ")}
-      {flag_acc}
-    }});{tl_pin}{TL(5)}
-    rn::wave_lds_sync();
-    if (on) rn::regs_to_lds<{EE}>(s_P, lane, P);
-    rn::wave_lds_sync();
-    rn::tile_l2g<{EE}>(gP + base * {EE}, cnt, s_P, lane);{cP_store}"""
-      else:
-        update = f"""int nf = 0;
-    int fl = update_{k.kind}_regs(x, P, z, R{ea});
-    {norm}{tl_pin}{TL(5)}
-    rn::wave_lds_sync();
-    if (on) {{
-      rn::regs_to_lds<{D}>(s_x, lane, x);
-      rn::regs_to_lds<{EE}>(s_P, lane, P);
-      rn::regs_to_lds<{Z}>(s_z, lane, z);
-    }}
-    rn::wave_lds_sync();
-    rn::tile_l2g<{D}>(gx + base * {D}, cnt, s_x, lane);
-    rn::tile_l2g<{EE}>(gP + base * {EE}, cnt, s_P, lane);
-    rn::tile_l2g<{Z}>(gz + base * {Z}, cnt, s_z, lane);{cx_store}{cP_store}
-    {{
-      {flag_acc}
-    }}"""
-      tl_decl = f"""
-    const bool tl_on = tile == blockIdx.x && blockIdx.x < 256;
-    unsigned long long tl_c[7] = {{0, 0, 0, 0, 0, 0, 0}}, tl_w[7] = {{0, 0, 0, 0, 0, 0, 0}};{TL(0)}""" if tline else ""
-      tl_out = f"""{TL(6)}
-    if (tl_on && lane == 0) {{
-#pragma unroll
-      for (int i = 0; i < 7; i++) {{ g_tl[(blockIdx.x * 8 + i) * 2] = tl_c[i]; g_tl[(blockIdx.x * 8 + i) * 2 + 1] = tl_w[i]; }}
-    }}""" if tline else ""
-      out.append(f"""
-// ---- kind {k.kind}: [predict +] update{" + checkpoint" if ckpt else ""}, state round-trips HBM once per launch --------------------------
-template <bool DO_PREDICT>
-__global__ __launch_bounds__(64){kattr} void {kn}(double* __restrict__ gx, double* __restrict__ gP,
-    double* __restrict__ gz, const double* __restrict__ gR, const int r_per_filter, const double* __restrict__ gea,
-    const double* __restrict__ gQ, const double* __restrict__ gdt, const double dt_scalar, const int64_t n,
-    const int norm_quats, uint8_t* __restrict__ flags, const uint8_t* __restrict__ active{cargs}) {{
-  __shared__ __attribute__((aligned(16))) double s_x[64 * {D | 1}];
-  __shared__ __attribute__((aligned(16))) double s_P[64 * {EE | 1}];
-  __shared__ __attribute__((aligned(16))) double s_z[64 * {Z | 1}];
-  __shared__ __attribute__((aligned(16))) double s_R[64 * {ZZ | 1}];
-  __shared__ __attribute__((aligned(16))) double s_Q[{EE}];
-  __shared__ __attribute__((aligned(16))) double s_dt[64];
-  const int lane = threadIdx.x;
-  if (DO_PREDICT) {{
-    for (int i = lane; i < {EE}; i += 64) s_Q[i] = gQ[i];
-  }}
-  const int64_t tiles = (n + 63) >> 6;
-  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {{
-    const int64_t base = tile << 6;
-    const int cnt = (n - base) < 64 ? (int)(n - base) : 64;{tl_decl}
-    // a shared R is requested in front of the tiles and first used behind the wait for all of them: an ordinary load, and at the first
-    // use of one hipcc waits for everything in flight
-    double R[{ZZ}];
-    if (!r_per_filter) {{
-#pragma unroll
-      for (int i = 0; i < {ZZ}; i++) R[i] = gR[i];
-    }}
-    {load}
-    const bool on = active == nullptr || (lane < cnt && act != 0);
-    {update}
-    if (flags != nullptr && lane < cnt) flags[base + lane] = (uint8_t)(on ? (fl | nf) : 16);{tl_out}
-    rn::wave_lds_sync();
-  }}
-}}
-""")
-  from rednose_amd.codegen import emit as _emit
-  if _emit.step_kinds(spec):
+  # k_stepc_{kind}: the same kernel writing a CHECKPOINT on its way -- the observations as they came (cz) and the filtered pair (cx, cP): what the
+  # orchestrators' rewind rings keep of every call (ekf_sym.cc:142-156, 191).  A kernel of its own, so that k_step_{kind} stays as it is.
+  knobs = dict(kattr=kattr, split=split, zwait=tune.small_zwait, tline=bool(tune.small_timeline))
+  out += [step_kernel(spec, norm, k, ckpt, **knobs) for k in spec.kinds for ckpt in (False, True)]
+  from rednose_amd.codegen import emit      # (emit imports this module: see its docstring)
+  if emit.step_kinds(spec):
     out.append(kinds_kernel(spec, norm, kattr, split))
   if run_block(spec) > 0:          # blocked fused runs: k_run_blk (no trace) and k_run_blk_tr (filtered trace)
     out.append(run_kernel_blk(spec, norm))
@@ -552,119 +457,188 @@ def kinds_kernel(spec, norm, kattr="", split=False):
   The load order is that of small_zwait == 1 (z last, counted wait) whatever the knob says -- the knob's alternatives exist for the per-kind
   kernels' A/B runs only --, s_R is allocated whether or not R comes per filter, and a shared R is read from the table inside the switch (one
   load per kind present in the wavefront).  This family's kernel is covered by tests; its time has not been measured."""
+  return step_kernel(spec, norm, None, kattr=kattr, split=split)
+
+
+def step_kernel(spec, norm, k, ckpt=False, kattr="", split=False, zwait=1, tline=False):
+  """The step kernels, [predict +] update with the state round-tripping HBM once per launch: k_step_{kind} of kind k, k_stepc_{kind} (ckpt: the same
+  writing the call's checkpoint), and with k = None k_kinds (see kinds_kernel; x, z and P leave together there, after the switch).
+  `zwait`, `split`, `tline`: the tuning knobs small_zwait, small_split, small_timeline."""
+  mixed = k is None
   D, E = spec.dim_x, spec.dim_err
   EE = E * E
-  zmax = max(k.zdim for k in spec.kinds)
-  ZZ = zmax * zmax
-  cases = []
-  for idx, k in enumerate(spec.kinds):
-    Z = k.zdim
-    call = (f"update_{k.kind}_regs_split(x, P, zk, Rk, []() {{}})" if split else f"update_{k.kind}_regs(x, P, zk, Rk)")
-    cases.append(f"""        case {k.kind}: {{
-          double zk[{Z}], Rk[{Z * Z}];
+  Z = max(kk.zdim for kk in spec.kinds) if mixed else k.zdim
+  ZZ = Z * Z
+  kn = "k_kinds" if mixed else (f"k_stepc_{k.kind}" if ckpt else f"k_step_{k.kind}")
+  cargs = ", double* __restrict__ cx, double* __restrict__ cP, double* __restrict__ cz" if ckpt else ""
+  cz_store = f"\n    {_tile_out(Z, 'cz', 's_z')}      // the observations, before the residuals take their place" if ckpt else ""
+  cx_store = f"\n    {_tile_out(D, 'cx', 's_x')}" if ckpt else ""
+  cP_store = f"\n    {_tile_out(EE, 'cP', 's_P')}" if ckpt else ""
+
+  # ---- the timeline stamps (small_timeline; tools/timeline.py small): shader cycles and the 100 MHz wall clock, in scalar registers
+  def TL(i):
+    return f"\n    if (tl_on) {{ tl_c[{i}] = __builtin_readcyclecounter(); tl_w[{i}] = wall_clock64(); }}" if tline else ""
+  tl_pin = "\n" + _pin(EE, "P") if tline else ""      # stamped builds: a phase's arithmetic ends at its stamp
+  tl_decl = f"""
+    const bool tl_on = tile == blockIdx.x && blockIdx.x < 256;
+    unsigned long long tl_c[7] = {{0, 0, 0, 0, 0, 0, 0}}, tl_w[7] = {{0, 0, 0, 0, 0, 0, 0}};{TL(0)}""" if tline else ""
+  tl_out = f"""{TL(6)}
+    if (tl_on && lane == 0) {{
 #pragma unroll
-          for (int i = 0; i < {Z}; i++) zk[i] = z[i];
-          if (r_per_filter) {{
-#pragma unroll
-            for (int i = 0; i < {Z * Z}; i++) Rk[i] = Rf[i];
-          }} else {{
-#pragma unroll
-            for (int i = 0; i < {Z * Z}; i++) Rk[i] = gR[{idx * ZZ} + i];
-          }}
-          fl = {call};
-#pragma unroll
-          for (int i = 0; i < {Z}; i++) z[i] = zk[i];
-          break;
-        }}""")
-  nl = chr(10)
-  return f"""
-// ---- a kind per filter: [predict +] update of kinds[i], state round-trips HBM once per launch whatever the mix of kinds ------------
-template <bool DO_PREDICT>
-__global__ __launch_bounds__(64){kattr} void k_kinds(double* __restrict__ gx, double* __restrict__ gP,
-    double* __restrict__ gz, const double* __restrict__ gR, const int r_per_filter, const int32_t* __restrict__ gkinds,
-    const double* __restrict__ gQ, const double* __restrict__ gdt, const double dt_scalar, const int64_t n,
-    const int norm_quats, uint8_t* __restrict__ flags, const uint8_t* __restrict__ active) {{
-  __shared__ __attribute__((aligned(16))) double s_x[64 * {D | 1}];
-  __shared__ __attribute__((aligned(16))) double s_P[64 * {EE | 1}];
-  __shared__ __attribute__((aligned(16))) double s_z[64 * {zmax | 1}];
-  __shared__ __attribute__((aligned(16))) double s_R[64 * {ZZ | 1}];
-  __shared__ __attribute__((aligned(16))) double s_Q[{EE}];
-  __shared__ __attribute__((aligned(16))) double s_dt[64];
-  const int lane = threadIdx.x;
-  if (DO_PREDICT) {{
-    for (int i = lane; i < {EE}; i += 64) s_Q[i] = gQ[i];
-  }}
-  const int64_t tiles = (n + 63) >> 6;
-  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {{
-    const int64_t base = tile << 6;
-    const int cnt = (n - base) < 64 ? (int)(n - base) : 64;
-    rn::tile_g2l_async<{D}>(gx + base * {D}, cnt, s_x, lane);
-    rn::tile_g2l_async<{EE}>(gP + base * {EE}, cnt, s_P, lane);
-    if (r_per_filter) rn::tile_g2l_async<{ZZ}>(gR + base * {ZZ}, cnt, s_R, lane);
-    if (DO_PREDICT && gdt != nullptr) lane_dt_request(gdt + base + (lane < cnt ? lane : cnt - 1), s_dt, lane);
-    rn::tile_g2l_async<{zmax}>(gz + base * {zmax}, cnt, s_z, lane);
-    // the mask and the kinds are requested behind the tiles: one round trip for all (see k_step_*)
+      for (int i = 0; i < 7; i++) {{ g_tl[(blockIdx.x * 8 + i) * 2] = tl_c[i]; g_tl[(blockIdx.x * 8 + i) * 2 + 1] = tl_w[i]; }}
+    }}""" if tline else ""
+
+  # ---- the tile's requests, and what reads them out of LDS
+  tile_x, tile_P, tile_z = _tile_in(D, "gx", "s_x"), _tile_in(EE, "gP", "s_P"), _tile_in(Z, "gz", "s_z")
+  tile_R = "if (r_per_filter) " + _tile_in(ZZ, "gR", "s_R")
+  # the per-filter dt rides with the tiles (LDS-DMA, clamped inside a ragged tile: a lane without a filter stores nothing)
+  tile_dt = "if (DO_PREDICT && gdt != nullptr) lane_dt_request(gdt + base + (lane < cnt ? lane : cnt - 1), s_dt, lane);"
+  mask_note = ("// the mask and the kinds are requested behind the tiles: one round trip for all (see k_step_*)" if mixed else """\
+// masked-out filters (active[i] == 0) pass through untouched: x, P and z leave as they came, flag bit 4 is set.  The mask is requested
+    // behind the tiles: hipcc turns it into a lane mask at once, i.e. waits for it and for everything in front of it -- one round trip for all""")
+  act = f"""
+    {mask_note}
     uint8_t act = 1;
-    if (active != nullptr) act = active[base + (lane < cnt ? lane : cnt - 1)];
-    const int kind = gkinds[base + (lane < cnt ? lane : cnt - 1)];
-    wait_but_tile<{zmax}>(cnt);
-    rn::wave_lds_sync();
-    double x[{D}], P[{EE}], z[{zmax}], Rf[{ZZ}];
-    const double dt = (DO_PREDICT && gdt != nullptr) ? lane_dt(s_dt, lane) : dt_scalar;
-    rn::lds_to_regs<{D}>(s_x, lane, x);
-    rn::lds_to_regs<{EE}>(s_P, lane, P);
-    if (DO_PREDICT) {{
+    if (active != nullptr) act = active[base + (lane < cnt ? lane : cnt - 1)];""" + ("""
+    const int kind = gkinds[base + (lane < cnt ? lane : cnt - 1)];""" if mixed else "")
+  regs = f"double x[{D}], P[{EE}], z[{Z}]{f', Rf[{ZZ}]' if mixed else ''};"
+  read_dt = "const double dt = (DO_PREDICT && gdt != nullptr) ? lane_dt(s_dt, lane) : dt_scalar;"
+  read_xP = f"""rn::lds_to_regs<{D}>(s_x, lane, x);
+    rn::lds_to_regs<{EE}>(s_P, lane, P);"""
+  read_zR = f"""rn::lds_to_regs<{Z}>(s_z, lane, z);
+    if (r_per_filter) rn::lds_to_regs<{ZZ}>(s_R, lane, {'Rf' if mixed else 'R'});"""
+  predict = f"""if (DO_PREDICT) {{
       predict_regs(x, P, s_Q, dt);
       {norm}
-    }}
-#pragma unroll
-    for (int i = 0; i < {D}; i++) rn::pin(x[i]);
-#pragma unroll
-    for (int i = 0; i < {EE}; i++) rn::pin(P[i]);
+    }}"""
+  if zwait == 1:
+    # z last, counted wait.  vmcnt retires in issue order, so the tile that may stay in flight goes last: the observations are first read by the
+    # update, after 42 LDS reads and the whole predict; in a stream they are also the slowest tile (a buffer nothing has touched since it was
+    # written: HBM, while x and P were written by the previous launch and sit in the L2 / Infinity Cache)
+    pin_note = "" if mixed else "\n    // (the predict's arithmetic ends here: without the pins hipcc sinks it below the wait, into the update's)"
+    load = f"""{tile_x}
+    {tile_P}
+    {tile_R}
+    {tile_dt}
+    {tile_z}{TL(1)}{act}
+    wait_but_tile<{Z}>(cnt);
+    rn::wave_lds_sync();{TL(2)}
+    {regs}
+    {read_dt}
+    {read_xP}
+    {predict}{pin_note}
+{_pin(D, "x")}
+{_pin(EE, "P")}{TL(4)}
     rn::async_wait();
+    rn::wave_lds_sync();{TL(3)}{cz_store}
+    {read_zR}"""
+  else:
+    # all tiles, one wait; 0: the observations first (they are the slowest tile, see above), 2: between x and P
+    order = [tile_z, tile_R, tile_x, tile_P] if zwait == 0 else [tile_x, tile_R, tile_z, tile_P]
+    nl = "\n    "
+    behind = (32 * D + 63) // 64 + (32 * EE + 63) // 64 if zwait == 0 else (32 * EE + 63) // 64      # 16-byte requests behind the observations'
+    tlw = f"\n    if (tl_on && cnt == 64) rn::async_wait_but<{behind}>();{TL(3)}" if tline else ""
+    load = f"""{nl.join(order)}
+    {tile_dt}{TL(1)}{act}{tlw}
+    rn::async_wait();
+    rn::wave_lds_sync();{TL(2)}{cz_store}
+    {regs}
+    {read_dt}
+    {read_xP}
+    {read_zR}
+    {predict}{tl_pin}{TL(4)}"""
+
+  # ---- the update and the write-back
+  x_z_out = f"""rn::wave_lds_sync();
+      if (on) {{
+        rn::regs_to_lds<{D}>(s_x, lane, x);
+        rn::regs_to_lds<{Z}>(s_z, lane, z);
+      }}
+      rn::wave_lds_sync();
+      {_tile_out(D, "gx", "s_x")}
+      {_tile_out(Z, "gz", "s_z")}"""
+  all_out = f"""rn::wave_lds_sync();
+    if (on) {{
+      rn::regs_to_lds<{D}>(s_x, lane, x);
+      rn::regs_to_lds<{EE}>(s_P, lane, P);
+      rn::regs_to_lds<{Z}>(s_z, lane, z);
+    }}
     rn::wave_lds_sync();
-    rn::lds_to_regs<{zmax}>(s_z, lane, z);
-    if (r_per_filter) rn::lds_to_regs<{ZZ}>(s_R, lane, Rf);
-    const bool live = lane < cnt && act != 0;
+    {_tile_out(D, "gx", "s_x")}
+    {_tile_out(EE, "gP", "s_P")}
+    {_tile_out(Z, "gz", "s_z")}{cx_store}{cP_store}
+    {{
+      {_flag_acc(D)}
+    }}"""
+  if mixed:
+    cases = kind_cases(spec, "_regs_split" if split else "_regs", "z", "Rf[i]", R_shared=lambda idx: f"gR[{idx * ZZ} + i]", extra=", []() {}" if split else "")
+    update = f"""const bool live = lane < cnt && act != 0;
     bool on = live;
     int fl = 0, nf = 0;
     if (live) {{
       switch (kind) {{
-{nl.join(cases)}
+{cases}
         default: on = false; break;      // not a kind of this model: untouched, flag 8
       }}
     }}
     {norm}
+    {all_out}"""
+  else:
+    # extra arguments are per observation, i.e. per filter of the batch: (n, len(ea)) row-major
+    ea = f", gea + (base + (lane < cnt ? lane : 0)) * {ea_count(k)}" if k.ea_sym is not None else ""
+    on = "const bool on = active == nullptr || (lane < cnt && act != 0);\n    int nf = 0;\n    "
+    if split:
+      # x and the residual are final before the Joseph form, the bulk of the update's arithmetic: they leave there, P follows alone
+      cx_store = cx_store.replace("\n    ", "\n      ")
+      update = f"""{on}int fl = update_{k.kind}_regs_split(x, P, z, R{ea}, [&]() {{
+      {norm}
+      {x_z_out}{cx_store}
+      {_flag_acc(D)}
+    }});{tl_pin}{TL(5)}
     rn::wave_lds_sync();
-    if (on) {{
-      rn::regs_to_lds<{D}>(s_x, lane, x);
-      rn::regs_to_lds<{EE}>(s_P, lane, P);
-      rn::regs_to_lds<{zmax}>(s_z, lane, z);
-    }}
+    if (on) rn::regs_to_lds<{EE}>(s_P, lane, P);
     rn::wave_lds_sync();
-    rn::tile_l2g<{D}>(gx + base * {D}, cnt, s_x, lane);
-    rn::tile_l2g<{EE}>(gP + base * {EE}, cnt, s_P, lane);
-    rn::tile_l2g<{zmax}>(gz + base * {zmax}, cnt, s_z, lane);
-    {{
-      double acc = 0.0;
+    {_tile_out(EE, "gP", "s_P")}{cP_store}"""
+    else:
+      update = f"""{on}int fl = update_{k.kind}_regs(x, P, z, R{ea});
+    {norm}{tl_pin}{TL(5)}
+    {all_out}"""
+  title = ("// ---- a kind per filter: [predict +] update of kinds[i], state round-trips HBM once per launch whatever the mix of kinds ------------" if mixed else
+           f"// ---- kind {k.kind}: [predict +] update{' + checkpoint' if ckpt else ''}, state round-trips HBM once per launch --------------------------")
+  shared_R = "" if mixed else f"""
+    // a shared R is requested in front of the tiles and first used behind the wait for all of them: an ordinary load, and at the first
+    // use of one hipcc waits for everything in flight
+    double R[{ZZ}];
+    if (!r_per_filter) {{
 #pragma unroll
-      for (int i = 0; i < {D}; i++) acc += x[i];
-      if (!(acc - acc == 0.0)) nf = 2;          // non-finite state
-    }}
-    if (flags != nullptr && lane < cnt) flags[base + lane] = (uint8_t)(on ? (fl | nf) : (live ? 8 : 16));
+      for (int i = 0; i < {ZZ}; i++) R[i] = gR[i];
+    }}"""
+  return f"""
+{title}
+template <bool DO_PREDICT>
+__global__ __launch_bounds__(64){kattr} void {kn}(double* __restrict__ gx, double* __restrict__ gP,
+    double* __restrict__ gz, const double* __restrict__ gR, const int r_per_filter, {'const int32_t* __restrict__ gkinds' if mixed else 'const double* __restrict__ gea'},
+    const double* __restrict__ gQ, const double* __restrict__ gdt, const double dt_scalar, const int64_t n,
+    const int norm_quats, uint8_t* __restrict__ flags, const uint8_t* __restrict__ active{cargs}) {{
+{_lds(x=D, P=EE, z=Z, R=ZZ)}
+{_lds(True, Q=EE, dt=64)}
+  const int lane = threadIdx.x;
+  if (DO_PREDICT) {{
+    for (int i = lane; i < {EE}; i += 64) s_Q[i] = gQ[i];
+  }}
+{TILE_LOOP}{tl_decl}{shared_R}
+    {load}
+    {update}
+    if (flags != nullptr && lane < cnt) flags[base + lane] = (uint8_t)(on ? (fl | nf) : {'(live ? 8 : 16)' if mixed else '16'});{tl_out}
     rn::wave_lds_sync();
   }}
 }}
 """
 
 
-def launch_kinds(do_predict):
-  tf = "true" if do_predict else "false"
-  args = ("x, P, z, R, r_per_filter, kinds, Q, dt_vec, dt, n, norm_quats, flags, active" if do_predict else
-          "x, P, z, R, r_per_filter, kinds, nullptr, nullptr, 0.0, n, norm_quats, flags, active")
-  return f"""  const int64_t tiles = (n + 63) >> 6;
-  hipLaunchKernelGGL(k_kinds<{tf}>, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
-                     {args});"""
+launch_predict, launch_step, launch_step_ckpt, launch_kinds = (functools.partial(f, TILES) for f in (
+  emit_common.launch_predict, emit_common.launch_step, emit_common.launch_step_ckpt, emit_common.launch_kinds))
+launch_maha = functools.partial(emit_common.launch_maha, TILES, ea=False)      # this family's k_maha_{kind} has no extra-argument parameter
 
 
 def run_unroll(spec):
@@ -677,7 +651,7 @@ def run_block(spec):
   """Steps per block of the untraced fused run (k_run_blk): observation rows of one block are in flight while the previous block is
   computed, so a block has to outlast one HBM round trip (~2 us); a step of the 2-state model takes ~0.1 us, of a 6-state model
   ~1 us.  Bounded by the staging registers (2 x K x zmax doubles per lane) and the code size (the K steps are unrolled)."""
-  from rednose_amd.codegen import emit
+  from rednose_amd.codegen import emit      # (emit imports this module: see its docstring)
   forced = -1 if "no_run_blk" in emit._active else tuning.current().run_block      # pylint: disable=protected-access
   if forced:
     return max(0, forced)
@@ -696,25 +670,7 @@ def run_kernel(spec, norm):
   EE = E * E
   zmax = max(k.zdim for k in spec.kinds)
   KP = run_unroll(spec)
-  cases = []
-  EAM = max([int(sp.Matrix(k.ea_sym).shape[0]) for k in spec.kinds if k.ea_sym is not None] + [0])
-  for k in spec.kinds:
-    Z = k.zdim
-    ea, guard = "", ""
-    if k.ea_sym is not None:      # per-filter, per-step extra arguments: the (T, n, EA) array of the entry point (flag 8 without it)
-      ea = f", gea + ((int64_t)t * n + base + (lane < cnt ? lane : 0)) * {EAM}"
-      guard = "          if (gea == nullptr) { fl = 8; break; }\n"
-    cases.append(f"""        case {k.kind}: {{
-{guard}          double zk[{Z}], Rk[{Z * Z}];
-#pragma unroll
-          for (int i = 0; i < {Z}; i++) zk[i] = z[i];
-#pragma unroll
-          for (int i = 0; i < {Z * Z}; i++) Rk[i] = gR[t * {zmax * zmax} + i];
-          fl = update_{k.kind}_regs_sym(x, P, zk, Rk{ea});
-#pragma unroll
-          for (int i = 0; i < {Z}; i++) z[i] = zk[i];
-          break;
-        }}""")
+  cases = kind_cases(spec, "_regs_sym", "z", f"gR[t * {zmax * zmax} + i]", ea_lane="(lane < cnt ? lane : 0)")
   return f"""
 // ---- fused multi-step run: kinds[t], dts[t] shared by all filters; z is (T, n, {zmax}) in: z, out: y -----------
 __global__ __launch_bounds__(64) void k_run(double* __restrict__ gx, double* __restrict__ gP, const double* __restrict__ gQ,
@@ -722,16 +678,11 @@ __global__ __launch_bounds__(64) void k_run(double* __restrict__ gx, double* __r
     const double* __restrict__ gR, const int64_t n, const int norm_quats, uint8_t* __restrict__ flags,
     double* __restrict__ tx, double* __restrict__ tP, const double* __restrict__ gea, const int32_t* __restrict__ augs) {{
   (void)gea; (void)augs;      // lane-per-filter models are never MSCKF models (those use the lane-group family): no window shift here
-  __shared__ __attribute__((aligned(16))) double s_x[64 * {D | 1}];
-  __shared__ __attribute__((aligned(16))) double s_P[64 * {EE | 1}];
-  __shared__ __attribute__((aligned(16))) double s_z[64 * {zmax | 1}];
-  __shared__ __attribute__((aligned(16))) double s_Q[{EE}];
+{_lds(x=D, P=EE, z=zmax)}
+{_lds(True, Q=EE)}
   const int lane = threadIdx.x;
   for (int i = lane; i < {EE}; i += 64) s_Q[i] = gQ[i];
-  const int64_t tiles = (n + 63) >> 6;
-  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {{
-    const int64_t base = tile << 6;
-    const int cnt = (n - base) < 64 ? (int)(n - base) : 64;
+{TILE_LOOP}
     rn::tile_g2l<{D}>(gx + base * {D}, cnt, s_x, lane);
     rn::tile_g2l<{EE}>(gP + base * {EE}, cnt, s_P, lane);
     rn::tile_g2l<{zmax}>(gz + base * {zmax}, cnt, s_z, lane);
@@ -762,7 +713,7 @@ __global__ __launch_bounds__(64) void k_run(double* __restrict__ gx, double* __r
       {norm}
       int fl = 0;
       switch (kind) {{
-{chr(10).join(cases)}
+{cases}
         default: fl = 8; break;      // kind not available in the fused run (unknown, or it takes extra arguments)
       }}
       {norm}
@@ -814,25 +765,7 @@ def run_kernel_blk(spec, norm, trace=False):
   ZZ = zmax * zmax
   K = run_block(spec)
   NR = (K * ZZ + 63) // 64
-  EAM = max([int(sp.Matrix(k.ea_sym).shape[0]) for k in spec.kinds if k.ea_sym is not None] + [0])
-  cases = []
-  for k in spec.kinds:
-    Z = k.zdim
-    ea, guard = "", ""
-    if k.ea_sym is not None:
-      ea = f", gea + ((int64_t)t * n + base + lc) * {EAM}"
-      guard = "            if (gea == nullptr) { fl = 8; break; }\n"
-    cases.append(f"""          case {k.kind}: {{
-{guard}            double zk[{Z}], Rk[{Z * Z}];
-#pragma unroll
-            for (int i = 0; i < {Z}; i++) zk[i] = cur[u][i];
-#pragma unroll
-            for (int i = 0; i < {Z * Z}; i++) Rk[i] = lane_bcast(Rv[(u * {ZZ} + i) >> 6], (u * {ZZ} + i) & 63);
-            fl = update_{k.kind}_regs_sym(x, P, zk, Rk{ea});
-#pragma unroll
-            for (int i = 0; i < {Z}; i++) cur[u][i] = zk[i];
-            break;
-          }}""")
+  cases = kind_cases(spec, "_regs_sym", "cur[u]", f"lane_bcast(Rv[(u * {ZZ} + i) >> 6], (u * {ZZ} + i) & 63)", ea_lane="lc", ind=10)
   # rows are addressed by pointer increments (one 64-bit multiply per block, none per row): a row past the end of the schedule
   # re-reads row T - 1 (the increment is zero there), so the loads stay unconditional
   issue = f"""{{
@@ -886,9 +819,8 @@ __global__ __launch_bounds__(64) void {kname}(double* __restrict__ gx, double* _
     const double* __restrict__ gR, const int64_t n, const int norm_quats, uint8_t* __restrict__ flags,
     const double* __restrict__ gea{targs}) {{
   (void)gea;
-  __shared__ __attribute__((aligned(16))) double s_x[64 * {D | 1}];
-  __shared__ __attribute__((aligned(16))) double s_P[64 * {EE | 1}];
-  __shared__ __attribute__((aligned(16))) double s_Q[{EE}];
+{_lds(x=D, P=EE)}
+{_lds(True, Q=EE)}
   const int lane = threadIdx.x;
   for (int i = lane; i < {EE}; i += 64) s_Q[i] = gQ[i];
   const int64_t tiles = (n + 63) >> 6;
@@ -950,7 +882,7 @@ __global__ __launch_bounds__(64) void {kname}(double* __restrict__ gx, double* _
           {norm}
           int fl = 0;
           switch (kind) {{
-{chr(10).join(cases)}
+{cases}
             default: fl = 8; break;      // kind not available in the fused run (unknown, or it takes extra arguments)
           }}
           {norm}
@@ -995,26 +927,3 @@ def launch_run(spec=None):
     hipLaunchKernelGGL(k_run_blk_tr, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
                        x, P, Q, kinds, dts, T, z, R, n, norm_quats, flags, ea, trace_x, trace_P);
   }"""
-
-
-def launch_predict():
-  return """  const int64_t tiles = (n + 63) >> 6;
-  hipLaunchKernelGGL(k_predict, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
-                     x, P, Q, dt_vec, dt, n, norm_quats, active);"""
-
-
-def launch_step_ckpt(kind):
-  return f"""  const int64_t tiles = (n + 63) >> 6;
-  hipLaunchKernelGGL(k_stepc_{kind}<true>, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
-                     x, P, z, R, r_per_filter, ea, Q, dt_vec, dt, n, norm_quats, flags, active, ckpt_x, ckpt_P, ckpt_z);"""
-
-
-def launch_step(kind, do_predict):
-  tf = "true" if do_predict else "false"
-  if do_predict:
-    args = "x, P, z, R, r_per_filter, ea, Q, dt_vec, dt, n, norm_quats, flags, active"
-  else:
-    args = "x, P, z, R, r_per_filter, ea, nullptr, nullptr, 0.0, n, norm_quats, flags, active"
-  return f"""  const int64_t tiles = (n + 63) >> 6;
-  hipLaunchKernelGGL(k_step_{kind}<{tf}>, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
-                     {args});"""

@@ -20,12 +20,12 @@ The algebra and its order are unchanged (see emit_wide.py / emit_small.py docstr
 scalars changed.  Results agree with the first structure to rounding (different instruction streams contract
 FMAs differently), which tests/test_gpu_run.py bounds.
 """
-import os
+import functools
 import re
 
 import sympy as sp
 
-from rednose_amd.codegen import tuning
+from rednose_amd.codegen import emit_common, tuning
 from rednose_amd.codegen.lower import Block, vector_names
 from rednose_amd.codegen.emit_common import SMat, term, sum_terms, innovation_solver
 
@@ -50,8 +50,7 @@ def filters_per_wave(spec):
 EADIM = 3        # extra-argument dimension of feature-track kinds, hard-coded in the reference (ekf_sym.py:151)
 
 
-def ea_dim(k):
-  return 0 if k.ea_sym is None else int(sp.Matrix(k.ea_sym).shape[0])
+ea_dim = emit_common.ea_count
 
 
 def _ind(lines, n=2):
@@ -817,8 +816,8 @@ def kernels(spec):
   for k in spec.kinds:
     out.append(kernel(f"k_step_{k.kind}", k))
     out.append(kernel(f"k_stepc_{k.kind}", k, ckpt=True))
-  from rednose_amd.codegen import emit as _emit
-  if _emit.step_kinds(spec):
+  from rednose_amd.codegen import emit      # (emit imports this module: see its docstring)
+  if emit.step_kinds(spec):
     out.append("""
 // Does any lane of the wavefront hold `p`?  (k_kinds skips the matrix update of a kind no filter of a pass has: an optimisation only, every
 // store of the matrix phase is predicated.  A host build of this text, the kernels running lane by lane as threads, takes every update.)
@@ -913,39 +912,6 @@ __global__ __launch_bounds__(64) void k_maha_{k.kind}(const double* __restrict__
   return "\n".join(out)
 
 
-def launch_maha(kind):
-  return f"""  const int64_t tiles = (n + FT2 - 1) / FT2;
-  hipLaunchKernelGGL(k_maha_{kind}, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
-                     x, P, z, R, r_per_filter, ea, n, d2);"""
-
-
-def launch_predict():
-  return """  const int64_t tiles = (n + FT2 - 1) / FT2;
-  hipLaunchKernelGGL(k_predict, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
-                     x, P, Q, dt_vec, dt, n, norm_quats, active);"""
-
-
-def launch_step(kind, do_predict):
-  tf = "true" if do_predict else "false"
-  if do_predict:
-    args = "x, P, z, R, r_per_filter, ea, Q, dt_vec, dt, n, norm_quats, flags, active"
-  else:
-    args = "x, P, z, R, r_per_filter, ea, nullptr, nullptr, 0.0, n, norm_quats, flags, active"
-  return f"""  const int64_t tiles = (n + FT2 - 1) / FT2;
-  hipLaunchKernelGGL(k_step_{kind}<{tf}>, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
-                     {args});"""
-
-
-def launch_step_ckpt(kind):
-  return f"""  const int64_t tiles = (n + FT2 - 1) / FT2;
-  hipLaunchKernelGGL(k_stepc_{kind}<true>, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
-                     x, P, z, R, r_per_filter, ea, Q, dt_vec, dt, n, norm_quats, flags, active, ckpt_x, ckpt_P, ckpt_z);"""
-
-
-def launch_kinds(do_predict):
-  tf = "true" if do_predict else "false"
-  args = ("x, P, z, R, r_per_filter, kinds, Q, dt_vec, dt, n, norm_quats, flags, active" if do_predict else
-          "x, P, z, R, r_per_filter, kinds, nullptr, nullptr, 0.0, n, norm_quats, flags, active")
-  return f"""  const int64_t tiles = (n + FT2 - 1) / FT2;
-  hipLaunchKernelGGL(k_kinds<{tf}>, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
-                     {args});"""
+TILES = "(n + FT2 - 1) / FT2"      # tiles of a launch: FT2 filters per wavefront (tile_filters)
+launch_predict, launch_step, launch_step_ckpt, launch_kinds, launch_maha = (functools.partial(f, TILES) for f in (
+  emit_common.launch_predict, emit_common.launch_step, emit_common.launch_step_ckpt, emit_common.launch_kinds, emit_common.launch_maha))

@@ -1,0 +1,89 @@
+#!/usr/bin/env python3
+"""sha256 of `{name}.h` / `{name}.hip` as emitted (nothing compiled: no GPU, no hipcc) over models x fallbacks x tuning knobs, a line each.
+A change to the emitters that must leave every generated text as it is: run it with --tree on the parent checkout and on the branch, compare.
+
+  python tools/emit_digest.py OUT.txt [--tree OTHER_CHECKOUT] [--jobs N]"""
+import argparse
+import hashlib
+import os
+import sys
+import tempfile
+from concurrent.futures import ProcessPoolExecutor
+
+KNOBS = ("small_zwait=0", "small_zwait=2", "small_split=0", "small_zwait=0,small_split=0", "small_timeline=1", "small_timeline=1,small_zwait=0",
+         "small_timeline=1,small_zwait=2,small_split=0", "small_waves=2", "run_block=-1")      # of the lane-per-filter step kernels
+FALLBACK_MODELS = {"force_wide": ("kinematic6", "attitude"), "no_run_blk": ("kinematic", "kinematic6"), "no_kinds": ("kinematic6", "kinematic9", "live"),
+                   "no_model_defaults": ("live", "feature36"), "no_run2": ("live",), "no_tri": ("live",), "no_rts4": ("live",), "rts_one_wave": ("live",),
+                   "no_rts": ("live",), "no_run": ("rand40", "feature36")}      # models on which the fallback changes the text
+GV_MODELS = ("gv_runtime", "gv_runtime10", "gv_extra")
+
+
+def configurations():
+  """-> [(model, RN_TUNE, fallback or None)]"""
+  import examples
+  from rednose_amd.codegen import emit
+  assert set(FALLBACK_MODELS) == set(emit.FALLBACKS), "a fallback without models in this matrix"
+  cfg = [(n, "", None) for n in examples.model_table()] + [(n, "exact_math=1", None) for n in examples.EXACT_NAMES]
+  cfg += [(n, "", fb) for fb in emit.FALLBACKS for n in FALLBACK_MODELS[fb]]
+  cfg += [(n, kn, None) for n in ("kinematic6", "attitude") for kn in KNOBS] + [("kinematic9", "wide_timeline=1", None)]
+  return cfg + [(n, "", None) for n in GV_MODELS]
+
+
+def gv_spec(name):
+  """The models of tests/test_global_vars.py: a run-time scalar (`set_gain`) in either kernel family, and an extra routine."""
+  import sympy as sp
+  from rednose_amd.codegen.spec import build_spec
+  n, gain = (10 if name.endswith("10") else 2), (sp.Float(1.0) if name == "gv_extra" else sp.Symbol("gain"))
+  state_sym, dt, other = sp.MatrixSymbol("state", n, 1), sp.Symbol("dt"), sp.MatrixSymbol("other", 2, 1)
+  state = sp.Matrix(state_sym)
+  rate = sp.Matrix([gain * state[i + 1, 0] if i < n - 1 else 0 for i in range(n)])
+  obs = [[sp.Matrix([state[0, 0] + (gain * state[n - 1, 0] if n > 2 else 0)]), 1, None]]
+  energy = sp.Matrix([[0.5 * state[1, 0]**2 + 9.81 * state[0, 0] + other[0, 0] * other[1, 0]]])
+  extra = dict(extra_routines=[("energy", energy, [state_sym, other])]) if name == "gv_extra" else dict(global_vars=[gain])
+  return build_spec(name, state + dt * rate, dt, state_sym, obs, n, n, **extra)
+
+
+class _Spec(Exception):
+  pass
+
+
+def example_spec(name):
+  """The FilterSpec the example's own generate_code() hands to the emitter (whatever it passes to gen_code): gen_code stops there."""
+  import examples
+  from rednose_amd.helpers import ekf_sym
+
+  def grab(spec, fallbacks=()):
+    raise _Spec(spec)
+  real, ekf_sym.emit = ekf_sym.emit, grab
+  try:
+    with tempfile.TemporaryDirectory() as d:
+      examples.model_table()[name](d)
+    raise RuntimeError(f"{name}: generate_code did not reach the emitter")
+  except _Spec as e:
+    return e.args[0]
+  finally:
+    ekf_sym.emit = real
+
+
+def digest(cfg):
+  from rednose_amd.codegen import emit
+  name, tune, fb = cfg
+  os.environ["RN_TUNE"] = tune
+  hdr, src = emit.emit(gv_spec(name) if name in GV_MODELS else example_spec(name), (fb,) if fb else ())
+  label = name + (f" RN_TUNE={tune}" if tune else "") + (f" fallback={fb}" if fb else "")
+  return f"{label}: h {hashlib.sha256(hdr.encode()).hexdigest()} hip {hashlib.sha256(src.encode()).hexdigest()}"
+
+
+if __name__ == "__main__":
+  ap = argparse.ArgumentParser(description=__doc__.split("\n", 1)[0])
+  ap.add_argument("out")
+  ap.add_argument("--tree", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."), help="checkout to take rednose_amd and examples from")
+  ap.add_argument("--jobs", type=int, default=4)
+  args = ap.parse_args()
+  tree = os.path.abspath(args.tree)
+  sys.path.insert(0, tree)
+  with ProcessPoolExecutor(args.jobs, initializer=sys.path.insert, initargs=(0, tree)) as ex:
+    lines = list(ex.map(digest, configurations()))
+  with open(args.out, "w", encoding="utf-8") as f:
+    f.write("\n".join(lines) + "\n")
+  print(f"{len(lines)} configurations -> {args.out}")
