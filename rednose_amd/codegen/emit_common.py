@@ -1,5 +1,6 @@
-"""Pieces shared by the kernel emitters: structured (sparse-at-generation-time) matrices, the per-routine device
-functions of the reference's scalar C ABI, and the launch text of the step-granular kernels (launch_*)."""
+"""Pieces shared by the kernel emitters: structured (sparse-at-generation-time) matrices, the per-filter scalar slot of the lane-group
+family (SlotLayout), the per-routine device functions of the reference's scalar C ABI, and the launch text of the step-granular
+kernels (launch_*)."""
 import sympy as sp
 
 from rednose_amd.codegen.lower import Block, vector_names
@@ -56,6 +57,42 @@ class SMat:
 
   def col_nz(self, j):
     return [(i, self.e[i][j]) for i in range(self.rows) if self.e[i][j] is not None]
+
+
+EADIM = 3        # extra-argument dimension of feature-track kinds, hard-coded in the reference (ekf_sym.py:151)
+
+
+def ind(lines, n=2):
+  pad = " " * n
+  return [pad + s for s in lines]
+
+
+class SlotLayout:
+  """Per-filter scalar slot in LDS (doubles) of the lane-group family: the OFF_* of the fields emit_wide2.scalar_functions addresses and the
+  stride SLOT.  A subclass says in pack() in which order and with which overlaps ITS fields are packed and returns the slot's length."""
+
+  def __init__(self, spec, f_vars, he_vars_by_kind):
+    self.zmax = max(k.zdim for k in spec.kinds)
+    self.nf = len(f_vars)
+    self.nh = max([len(v) for v in he_vars_by_kind.values()] + [0])
+    self.zf = max([k.zdim for k in spec.kinds if k.He_sym is not None] + [0])      # rows of the feature-track kinds (MSCKF), 0: none
+    self.OFF_X = 0
+    n = self.pack(spec.dim_x, spec.dim_err)
+    self.SLOT = n if n & 1 else n + 1      # odd stride: lane-per-filter ds_*_b64 accesses hit 32 distinct bank pairs
+
+  def pack(self, D, E):
+    raise NotImplementedError
+
+  def feature_tail(self, n):
+    """Appends the fields of feature-track kinds at n -> the slot's length.  EADIM Householder reflectors of the extra-argument Jacobian
+    (EADIM x Z entries + EADIM betas: OFF_RF), the projected noise (Z - EADIM)^2 (OFF_RP), and the residual a second time: it exists in the
+    orthonormal basis of the reflectors (what the update consumes: OFF_YP) and in the reference's fullPivLu basis (what goes back into z:
+    the Y field)."""
+    zp = self.zf - EADIM
+    self.OFF_RF = n
+    self.OFF_RP = self.OFF_RF + (EADIM * self.zf + EADIM if self.zf else 0)
+    self.OFF_YP = self.OFF_RP + (zp ** 2 if self.zf else 0)
+    return self.OFF_YP + (zp if self.zf else 0)
 
 
 def ea_count(k):

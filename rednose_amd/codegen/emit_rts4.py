@@ -46,7 +46,8 @@ included: live, kinematic9); every other lane-group model -- MSCKF, more states,
 keeps rn::k_rts_group, which is also the fallback (`no_rts4`).  (k_rts3, the round-4 smoother in the fused run's layout, served the
 odd counts until round 6 and is gone.)
 """
-from rednose_amd.codegen.emit_common import term, sum_terms
+from rednose_amd.codegen import emit_wide2 as w2, tuning
+from rednose_amd.codegen.emit_common import SlotLayout, ind, term, sum_terms
 
 GL = 16            # lanes per filter: one DPP row
 FPW = 4            # filters per wavefront
@@ -72,11 +73,6 @@ MACROS = r"""
 """
 
 
-def _ind(lines, n=2):
-  pad = " " * n
-  return [pad + s for s in lines]
-
-
 def rows_per_lane(spec):
   return -(-spec.dim_err // GL)
 
@@ -91,51 +87,25 @@ def tri_applicable(spec):
   """k_rts4_tri (the packed-triangle trace, see kernel()) needs E (E + 1) / 2 more bytes of LDS under the same budget."""
   if not applicable(spec):
     return False
-  lay, _ = _tables(spec)
+  lay = w2.slot_tables(spec, RtsLayout, with_obs=False)[0]
   return lds_bytes(spec, lay.SLOT, tri=True) <= LDS_BUDGET
 
 
-class RtsLayout:
+class RtsLayout(SlotLayout):
   """Scalar slot of the smoother (doubles per filter): x' = f(x) [normalised], the non-trivial entries of F, dt."""
 
-  def __init__(self, spec, f_vars, he_vars_by_kind):        # same constructor as emit_wide2.Layout / emit_wide3.RunLayout
-    D = spec.dim_x
-    self.zmax = max(k.zdim for k in spec.kinds)
-    self.nf = len(f_vars)
-    self.nh = 0
-    self.OFF_X = 0
+  def pack(self, D, E):
+    self.nh = self.zf = 0
     self.OFF_F = D
     self.OFF_DT = D + self.nf
     n = self.OFF_DT + 1
-    # fields the shared scalar functions of emit_wide2.device_functions address but the smoother never calls
+    # fields the shared scalar functions of emit_wide2.scalar_functions address but the smoother never calls
     self.OFF_HE = self.OFF_DX = self.OFF_Y = self.OFF_FL = self.OFF_RF = self.OFF_RP = self.OFF_YP = n
-    self.zf = 0
-    self.SLOT = n + 1 - (n & 1)
-
-
-def _tables(spec):
-  from rednose_amd.codegen import emit_wide2 as w2
-  _, _, F, f_vars = w2._lowered_predict(spec)                  # pylint: disable=protected-access
-  lay = RtsLayout(spec, f_vars, {})
-  return lay, w2._slotted(F, f_vars, lay.OFF_F)                # pylint: disable=protected-access
-
-
-def _scal_text(spec):
-  """scal_predict against RtsLayout under the suffix _s (only that function of emit_wide2.device_functions is used)."""
-  from rednose_amd.codegen import emit_wide2 as w2
-  text, lay = w2.device_functions(spec, lay_cls=RtsLayout, sfx="_s")
-  # keep scal_predict_s only: the observation / injection functions address slot fields the smoother does not have
-  keep = []
-  for fn in text.split("\n\n"):
-    if "void scal_predict_s(" in fn:
-      keep.append(fn)
-  assert len(keep) == 1
-  return keep[0], lay
+    return n
 
 
 def dt0_path(spec):
   """Steps with dt == 0 take the identity-gain path (see kernel()): only for models whose predict(dt = 0) is the identity symbolically."""
-  from rednose_amd.codegen import tuning
   return bool(tuning.current().rts_dt0) and spec.identity_at_dt0()
 
 
@@ -147,7 +117,7 @@ def applicable(spec):
   E = spec.dim_err
   if E < 8 or E > 2 * GL:
     return False
-  lay, _ = _tables(spec)
+  lay = w2.slot_tables(spec, RtsLayout, with_obs=False)[0]
   return lds_bytes(spec, lay.SLOT) <= LDS_BUDGET
 
 
@@ -166,9 +136,8 @@ def kernel(spec, tri=False):
   S = range(R)
   RS = -(-E // R)        # rows per slot: row r lives in slot r // RS of lane r % RS (22 states: 2 x 11 -- balanced slots keep the block lower
                          # triangles of the symmetric matrices at 11 + 22 columns per lane instead of 16 + 22, and lanes RS .. 15 idle)
-  scal, lay = _scal_text(spec)
-  _, Fs = _tables(spec)
-  scal = scal.replace("scal_predict_s(", "scal_predict_s4(")
+  lay, Fs, _, low = w2.slot_tables(spec, RtsLayout, with_obs=False)
+  scal, = w2.scalar_functions(spec, lay, low, sfx="_s4", only=("scal_predict",))      # the only scalar phase the smoother calls
   quat = "".join(f" rn::normalize_quat<{D}>(xv, {q});" for q in spec.quaternion_idxs)
   b = []
   # Issue priority: the two E^3 products (stamps 7 .. 9) are straight FMA streams that can run any time; everything else in a step is a chain of

@@ -36,8 +36,8 @@ of the fused run apply unchanged (tests/test_gpu_run.py, test_gpu_random.py, tes
 tests/test_emit_host.py runs the kernel on the host with a thread per lane of both wavefronts.
 Reference: EKF_sym.predict_and_update_batch's loop body, ekf_sym.py:473-538, over a schedule; ekf_c.c:8-121.
 """
-from rednose_amd.codegen import emit_wide3 as w3
-from rednose_amd.codegen.emit_common import term, sum_terms
+from rednose_amd.codegen import emit_wide2 as w2, emit_wide3 as w3, tuning
+from rednose_amd.codegen.emit_common import SlotLayout, ind, term, sum_terms
 
 LDS_BUDGET = 40960      # bytes per workgroup for four workgroups per CU (160 KB)
 MIN_E = 13              # smallest number of error states served (measured, see applicable())
@@ -55,30 +55,24 @@ def layout2(spec):
   return 8, -(-E // 8), 8, 1
 
 
-class Run2Layout:
+class Run2Layout(SlotLayout):
   """Per-filter slot (doubles): [x] [F | dx] [He] [z / y] [dt] [flags].  F and He cannot share a region as in emit_wide3.RunLayout
   (both are live between B1 and B2); the room comes from the G / K^T buffer, which lives in the filter's covariance image here."""
 
-  def __init__(self, spec, f_vars, he_vars_by_kind):
-    D, E = spec.dim_x, spec.dim_err
-    self.zmax = max(k.zdim for k in spec.kinds)
-    self.nf = len(f_vars)
-    self.nh = max([len(v) for v in he_vars_by_kind.values()] + [0])
-    self.OFF_X = 0
+  def pack(self, D, E):
     self.OFF_F = self.OFF_DX = D
     self.OFF_HE = D + max(self.nf, E)
     self.OFF_Y = self.OFF_HE + self.nh
     self.OFF_DT = self.OFF_Y + self.zmax
     self.OFF_FL = self.OFF_DT + 1
     self.OFF_RF = self.OFF_RP = self.OFF_YP = -(1 << 20)      # feature-track kinds stay with k_run (applicable())
-    n = self.OFF_FL + 1
-    self.SLOT = n + 1 - (n & 1)
+    return self.OFF_FL + 1
 
 
 def lds_bytes(spec):
   E = spec.dim_err
   FPW = FPG
-  lay, _, _ = w3._tables(spec, Run2Layout)      # pylint: disable=protected-access
+  lay = w2.slot_tables(spec, Run2Layout)[0]
   zmax = max(k.zdim for k in spec.kinds)
   return 8 * (FPW * E * E + 2 + FPW * lay.SLOT + E + (E & 1)) + 16
 
@@ -90,7 +84,6 @@ def applicable(spec):
   FPW = FPG
   zmax = max(k.zdim for k in spec.kinds)
   plain = all(k.He_sym is None and k.ea_sym is None for k in spec.kinds)
-  from rednose_amd.codegen import tuning
   # below 13 error states k_run already has several wavefronts per SIMD and the second wavefront only adds barriers: kinematic9 (E = 9) 7.02 ms
   # with k_run against 8.04 with k_run2, rand13 21.3 against 18.2, rand17 34.9 against 31.0 (tools/ab_run, 32 768 filters x 1 000 steps;
   # profiles/r5_run2_small_models_ab.txt)
@@ -102,14 +95,8 @@ JB = 4            # columns per block of the rank-Z passes (2: 19.0 ms per confi
 CH = 8            # entries of a row of A = P F^T formed per block (and row slot) of predict (4: 19.0 ms, 8: 18.8)
 
 
-def _ind(lines, n=2):
-  pad = " " * n
-  return [pad + x for x in lines]
-
-
 def _tl(ph, base="tlb"):
   """Debug stamp (tuning knob wide_timeline; tools/timeline.py run2): slot `base` + ph of the workgroup's timeline, lane 0 of the calling wavefront."""
-  from rednose_amd.codegen import tuning
   if not tuning.current().wide_timeline:
     return []
   return [f"if ((threadIdx.x == 0 || threadIdx.x == blockDim.x - 64) && blockIdx.x < 256) {{ const int ti_ = {base} + {ph}; g_tl[(blockIdx.x * 64 + ti_) * 2] = __builtin_readcyclecounter(); "
@@ -117,7 +104,6 @@ def _tl(ph, base="tlb"):
 
 
 def _tl_on():
-  from rednose_amd.codegen import tuning
   return bool(tuning.current().wide_timeline)
 
 
@@ -129,7 +115,7 @@ def predict_fn(spec):
   registers beside the 132 of the rows."""
   E = spec.dim_err
   GL, R, _, _ = layout2(spec)
-  lay, Fs, _ = w3._tables(spec, Run2Layout)      # pylint: disable=protected-access
+  lay, Fs, _, _ = w2.slot_tables(spec, Run2Layout)
   b = [f"const double dt = sl[{lay.OFF_DT}];"]
   def shared(rows_of_f, blk):
     """Declarations of the slot-resident entries of F that the rows `rows_of_f` touch (one broadcast read each, used by every row slot),
@@ -193,7 +179,7 @@ def predict_fn(spec):
   rows = ", ".join(f"double (&row{s_})[{E}]" for s_ in range(R))
   idx = ", ".join(f"const int rr{s_}, const int rc{s_}, const bool ok{s_}" for s_ in range(R))
   head = f"__device__ __forceinline__ void predict_rows_r2({rows}, double* sP, const double* sQd, const double* __restrict__ gQ, const bool qdiag, const double* sl, {idx}) {{"
-  return "\n".join([head] + _ind(b) + ["}"])
+  return "\n".join([head] + ind(b) + ["}"])
 
 
 def update_fn(spec):
@@ -206,7 +192,7 @@ def update_fn(spec):
   a flag (`he_release`) after the Joseph coefficients tells it that He and y are dead."""
   E = spec.dim_err
   _, R, _, _ = layout2(spec)
-  lay, _, Hss = w3._tables(spec, Run2Layout)      # pylint: disable=protected-access
+  lay, _, Hss, _ = w2.slot_tables(spec, Run2Layout)
   ZM = lay.zmax
   b = ["(void)sP;"]
   for s_ in range(R):
@@ -252,7 +238,7 @@ def update_fn(spec):
   b += _tl(4)
   b.append("rn::wg_barrier();      // B3: dx, flags -> the scalar wavefront")
   b += _tl(5)
-  b += w3._rank_pass(E, ZM, R, "sG", "-=", "kk", JB=JB)      # pylint: disable=protected-access
+  b += w3.rank_pass(E, ZM, R, "sG", "-=", "kk", JB=JB)
   b += _tl(6)
   for s_ in range(R):
     b.append(f"double cc{s_}[{ZM}] = {{{', '.join('0.0' for _ in range(ZM))}}};")
@@ -276,13 +262,13 @@ def update_fn(spec):
   for s_ in range(R):
     b.append(f"if (ok{s_}) {{ " + " ".join(f"sG[{zi} * {E} + rr{s_}] = kk{s_}[{zi}];" for zi in range(ZM)) + " }")
   b.append("rn::wave_lds_sync();")
-  b += w3._rank_pass(E, ZM, R, "sG", "+=", "Dm", JB=JB)      # pylint: disable=protected-access
+  b += w3.rank_pass(E, ZM, R, "sG", "+=", "Dm", JB=JB)
   b.append("rn::wave_lds_sync();      // the broadcast buffer is free again")
   rows = ", ".join(f"double (&row{s_})[{E}]" for s_ in range(R))
   idx = ", ".join(f"const int rr{s_}, const int rc{s_}, const bool ok{s_}" for s_ in range(R))
   head = (f"__device__ __forceinline__ void update_rows_r2(const int kind, {rows}, const double* __restrict__ gR, double* sP, "
           f"double* sG, const double* sl, double* sw, {idx}, const int he_release, int* he_flag{', const int tlb' if _tl_on() else ''}) {{")
-  return "\n".join([head] + _ind(b) + ["}"])
+  return "\n".join([head] + ind(b) + ["}"])
 
 
 def kernels(spec, tri=False):
@@ -317,12 +303,11 @@ TRI_MACRO = r"""
 
 def run_kernel(spec, tri=False):
   """tri=True: `k_run2_tri`, the same kernel whose covariance trace is the packed lower triangle (trace_P: (T, n, E (E + 1) / 2))."""
-  from rednose_amd.codegen import tuning
   D, E = spec.dim_x, spec.dim_err
   EE = E * E
   TRI = E * (E + 1) // 2
   GL, R, FPW, ND = layout2(spec)
-  lay, _, _ = w3._tables(spec, Run2Layout)      # pylint: disable=protected-access
+  lay = w2.slot_tables(spec, Run2Layout)[0]
   zmax = max(k.zdim for k in spec.kinds)
   rows = ", ".join(f"row{s}" for s in range(R))
   idx = ", ".join(f"rr{s}, rc{s}, ok{s}" for s in range(R))

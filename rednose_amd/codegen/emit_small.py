@@ -35,13 +35,9 @@ import sympy as sp
 from rednose_amd.codegen import emit_common, tuning
 from rednose_amd.codegen.lower import Block, vector_names
 from rednose_amd.codegen.emit_common import SMat, term, sum_terms, innovation_solver, ea_count
+from rednose_amd.codegen.emit_common import ind as _ind
 
 TILES = "(n + 63) >> 6"      # tiles of a launch: 64 filters per wavefront
-
-
-def _ind(lines, n=2):
-  pad = " " * n
-  return [pad + s for s in lines]
 
 
 def predict_regs(spec, sym=False):

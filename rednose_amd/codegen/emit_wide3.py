@@ -28,24 +28,12 @@ test_gpu_random.py, test_gpu_msckf.py, test_gpu_fullsize.py bound it.  Measureme
 (The same layout for the step-granular entry points was built in round 2 and measured slower than the three-phase kernels of
 emit_wide2 -- one wavefront per SIMD cannot overlap its own HBM round trip; numbers in profiles/tuning_notes.md.)
 """
-import sympy as sp
-
-from rednose_amd.codegen.emit_common import term, sum_terms
-
-EADIM = 3        # extra-argument dimension of feature-track kinds, hard-coded in the reference (ekf_sym.py:151)
-
-
-def _ind(lines, n=2):
-  pad = " " * n
-  return [pad + s for s in lines]
-
-
-def ea_dim(k):
-  return 0 if k.ea_sym is None else int(sp.Matrix(k.ea_sym).shape[0])
+from rednose_amd.codegen import emit_wide2 as w2, tuning
+from rednose_amd.codegen.emit_common import EADIM, SlotLayout, ea_count, ind, term, sum_terms
 
 
 def ea_max(spec):
-  return max([ea_dim(k) for k in spec.kinds] + [0])
+  return max([ea_count(k) for k in spec.kinds] + [0])
 
 
 def layout(spec):
@@ -59,7 +47,6 @@ def layout(spec):
 
 def _tl(ph):
   """Debug stamp inside the matrix phases (tuning knob wide_timeline): slot 20 * (t % 3) + ph of the workgroup's timeline."""
-  from rednose_amd.codegen import tuning
   if not tuning.current().wide_timeline:
     return []
   return [f"if (threadIdx.x == 0 && blockIdx.x < 256) {{ const int ti_ = tl_t * 20 + {ph}; g_tl[(blockIdx.x * 64 + ti_) * 2] = "
@@ -67,13 +54,12 @@ def _tl(ph):
 
 
 def _tl_arg(call=False):
-  from rednose_amd.codegen import tuning
   if not tuning.current().wide_timeline:
     return ""
   return ", (int)(t % 3)" if call else ", const int tl_t"
 
 
-def _rank_pass(E, Z, R, src, op, coef, JB=None):
+def rank_pass(E, Z, R, src, op, coef, JB=None):
   """Straight-line rank-Z pass over the register rows: row_s[j] op= sum_z coef_s[z] * src[z][j] for all j, in blocks of JB
   columns.  Two things hipcc does not do by itself here:
     * the broadcast operands of block b + 1 are loaded before the FMAs of block b and a compiler fence closes every block, so
@@ -82,7 +68,6 @@ def _rank_pass(E, Z, R, src, op, coef, JB=None):
     * inside a block the FMAs are emitted term by term ACROSS the block's JB * R entries, so consecutive instructions belong to
       different accumulation chains: a dependent fp64 FMA issues ~40 cycles after its predecessor with one wavefront per SIMD
       (tools/fp64_ilp.hip), entry-by-entry order made every FMA wait for the one before it."""
-  from rednose_amd.codegen import tuning
   JB = JB or 4      # columns per block (6 and 8 measured in round 5: 21.21 / 20.90 ms per config-4 chunk against 21.04 / 21.24 -- noise; profiles/tuning_notes.md)
   out = []
   blocks = [list(range(j, min(j + JB, E))) for j in range(0, E, JB)]
@@ -100,45 +85,22 @@ def _rank_pass(E, Z, R, src, op, coef, JB=None):
           out.append(f"row{s}[{j}] {sg} {coef}{s}[{zi}]*q_{zi}_{j};")
     out.append(" ".join(f"rn::pin(row{s}[{j}]);" for j in bl for s in range(R)))
     out.append("rn::wave_lds_sync();")
-  return ["{"] + _ind(out) + ["}"]
+  return ["{"] + ind(out) + ["}"]
 
 
-class RunLayout:
+class RunLayout(SlotLayout):
   """Per-filter scalar slot of the fused run (doubles).  Same fields as emit_wide2.Layout, packed by lifetime so that eight
   filters of a 22-state model, their covariance images and the G / K^T buffers stay under 40 KB (4 wavefronts per CU):
   the non-trivial entries of F (dead once predict's matrix phase is through), those of He = H H_mod (written after that, dead
   once the Joseph-form coefficients exist) and dx (written after that) share one region; x lives ONLY here (no separate
   copy), and z comes in / y goes out through the Y field."""
 
-  def __init__(self, spec, f_vars, he_vars_by_kind):
-    D, E = spec.dim_x, spec.dim_err
-    self.zmax = max(k.zdim for k in spec.kinds)
-    self.nf = len(f_vars)
-    self.nh = max([len(v) for v in he_vars_by_kind.values()] + [0])
-    self.OFF_X = 0
+  def pack(self, D, E):
     self.OFF_F = self.OFF_HE = self.OFF_DX = D
     self.OFF_Y = D + max(self.nf, self.nh, E)
     self.OFF_DT = self.OFF_Y + self.zmax
     self.OFF_FL = self.OFF_DT + 1
-    feat = [k for k in spec.kinds if k.He_sym is not None]
-    self.zf = max([k.zdim for k in feat] + [0])
-    self.OFF_RF = self.OFF_FL + 1
-    self.OFF_RP = self.OFF_RF + (EADIM * self.zf + EADIM if feat else 0)
-    self.OFF_YP = self.OFF_RP + ((self.zf - EADIM) ** 2 if feat else 0)      # (see emit_wide2.Layout: the residual in the reflectors' basis, the elimination's work space)
-    n = self.OFF_YP + ((self.zf - EADIM) if feat else 0)
-    self.SLOT = n + 1 - (n & 1)      # odd stride, as in the step kernels
-
-
-def _tables(spec, lay_cls=None):
-  """Slot layout and slot-addressed coefficient matrices; the phase-1 / phase-3 functions are emit_wide2's, instantiated
-  against RunLayout under the suffix _r (emit_run2 passes its own layout class)."""
-  from rednose_amd.codegen import emit_wide2 as w2
-  _, _, F, f_vars = w2._lowered_predict(spec)                  # pylint: disable=protected-access
-  obs = {k.kind: w2._lowered_obs(spec, k) for k in spec.kinds}  # pylint: disable=protected-access
-  lay = (lay_cls or RunLayout)(spec, f_vars, {kk: v[3] for kk, v in obs.items()})
-  Fs = w2._slotted(F, f_vars, lay.OFF_F)                        # pylint: disable=protected-access
-  Hs = {kk: w2._slotted(v[2], v[3], lay.OFF_HE) for kk, v in obs.items()}   # pylint: disable=protected-access
-  return lay, Fs, Hs
+    return self.feature_tail(self.OFF_FL + 1)
 
 
 def predict_fn(spec, qdiag=False):
@@ -156,7 +118,7 @@ def predict_fn(spec, qdiag=False):
   middle of a step (profiles/r3a: 11.6 us per step with the trace against 8.7 without)."""
   E = spec.dim_err
   GL, R, _ = layout(spec)
-  lay, Fs, _ = _tables(spec)
+  lay, Fs, _, _ = w2.slot_tables(spec, RunLayout)
   b = [f"const double dt = sl[{lay.OFF_DT}];"]
   # rows of A, whole rows at a time: 16-byte LDS stores of a lane's contiguous row (entry-wise 8-byte stores at a row stride
   # collide on banks)
@@ -203,7 +165,7 @@ def predict_fn(spec, qdiag=False):
     head = (f"__device__ __forceinline__ void predict_rows_qd({rows}, double* sP, {qarg}, const double* sl, {idx}{_tl_arg()}) {{")
   else:
     head = (f"__device__ __forceinline__ void predict_rows({rows}, double* sP, const double* __restrict__ gQ, const double* sl, {idx}{_tl_arg()}) {{")
-  return "\n".join([head] + _ind(b) + ["}"])
+  return "\n".join([head] + ind(b) + ["}"])
 
 
 def update_fn(spec, k):
@@ -212,7 +174,7 @@ def update_fn(spec, k):
   the gate / rank flags go back to it."""
   E, Zf = spec.dim_err, k.zdim
   _, R, _ = layout(spec)
-  lay, _, Hss = _tables(spec)
+  lay, _, Hss, _ = w2.slot_tables(spec, RunLayout)
   Hs = Hss[k.kind]
   feat = k.He_sym is not None
   Z = Zf - EADIM if feat else Zf
@@ -262,7 +224,7 @@ def update_fn(spec, k):
     b.append(f"const double dx{s} = " + " + ".join(f"kk{s}[{zi}]*sl[{(lay.OFF_YP if feat else lay.OFF_Y) + zi}]" for zi in range(Z)) + ";")
   # B = P - K G: every broadcast row of G feeds all R row slots
   b += _tl(12)
-  b += _rank_pass(E, Z, R, "sG", "-=", "kk")
+  b += rank_pass(E, Z, R, "sG", "-=", "kk")
   b += _tl(13)
   for s in range(R):
     if feat:
@@ -280,14 +242,14 @@ def update_fn(spec, k):
              (f" if (rr{s} == 0) sw[{lay.OFF_FL}] = {fl};" if s == 0 else "") + " }")
   b.append("rn::wave_lds_sync();")
   b += _tl(14)
-  b += _rank_pass(E, Z, R, "sG", "+=", "Dm")
+  b += rank_pass(E, Z, R, "sG", "+=", "Dm")
   b += _tl(15)
   b.append("rn::wave_lds_sync();      // the broadcast buffer is free again")
   rows = ", ".join(f"double (&row{s})[{E}]" for s in range(R))
   idx = ", ".join(f"const int rr{s}, const int rc{s}, const bool ok{s}" for s in range(R))
   head = (f"__device__ __forceinline__ void update_{k.kind}_rows({rows}, const double* __restrict__ gR, double* sP, "
           f"double* sG, const double* sl, double* sw, {idx}{_tl_arg()}) {{")
-  return "\n".join([head] + _ind(b) + ["}"])
+  return "\n".join([head] + ind(b) + ["}"])
 
 
 def kernels(spec, with_run=True):
@@ -310,11 +272,10 @@ def kernels(spec, with_run=True):
 
 
 def run_kernel(spec):
-  from rednose_amd.codegen import tuning
   D, E = spec.dim_x, spec.dim_err
   EE = E * E
   GL, R, FPW = layout(spec)
-  lay, _, _ = _tables(spec)
+  lay = w2.slot_tables(spec, RunLayout)[0]
   zmax = max(k.zdim for k in spec.kinds)
   # observation entries a lane carries between HBM and the slots: FPW * zmax values per tile and step, one per lane and pass
   # (a single pass up to 8-dimensional observations at 8 filters per wavefront; the reference puts no limit on ZDIM, ekf_c.c:37)
@@ -344,7 +305,7 @@ def run_kernel(spec):
   idx = ", ".join(f"rr{s}, rc{s}, ok{s}" for s in range(R))
   scal_cases, mat_cases = [], []
   for k in spec.kinds:
-    EA = ea_dim(k)
+    EA = ea_count(k)
     feat = k.He_sym is not None
     args = f"sl, sl + {lay.OFF_Y}"
     guard = ""

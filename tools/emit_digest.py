@@ -16,6 +16,12 @@ FALLBACK_MODELS = {"force_wide": ("kinematic6", "attitude"), "no_run_blk": ("kin
                    "no_model_defaults": ("live", "feature36"), "no_run2": ("live",), "no_tri": ("live",), "no_rts4": ("live",), "rts_one_wave": ("live",),
                    "no_rts": ("live",), "no_run": ("rand40", "feature36")}      # models on which the fallback changes the text
 GV_MODELS = ("gv_runtime", "gv_runtime10", "gv_extra")
+LANE_GROUP_KNOBS = {      # of the lane-group family: the branches of its step kernels, the fused runs and the smoother that no default model takes
+  "live": ("wide_timeline=1", "wide_lean_q=0", "wide_inline=0", "wide_db=1,wide_ft=16", "wide_lean=0,wide_lb=0,wide_db=-1,wide_ft=0", "run2_prio=3",
+           "nt_trace=0", "rts_dt0=0", "tri_trace=0", "run2=0", "rts4=0"),
+  "kinematic9": ("wide_fpw=2", "wide_db=1", "wide_lean=1", "wide_lean=1,wide_lean_q=1", "wide_ft=8,wide_lb=2"),
+  "rand13": ("wide_timeline=1",), "rand17": ("wide_timeline=1",), "rand24": ("wide_timeline=1",),
+  "feature": ("wide_lean=1",), "feature36": ("wide_ft=8",), "randz10": ("wide_lean=1",)}
 
 
 def configurations():
@@ -26,7 +32,8 @@ def configurations():
   cfg = [(n, "", None) for n in examples.model_table()] + [(n, "exact_math=1", None) for n in examples.EXACT_NAMES]
   cfg += [(n, "", fb) for fb in emit.FALLBACKS for n in FALLBACK_MODELS[fb]]
   cfg += [(n, kn, None) for n in ("kinematic6", "attitude") for kn in KNOBS] + [("kinematic9", "wide_timeline=1", None)]
-  return cfg + [(n, "", None) for n in GV_MODELS]
+  cfg += [(n, "", None) for n in GV_MODELS]      # appended to, never reordered: earlier digest files stay a prefix of later ones
+  return cfg + [(n, kn, None) for n, knobs in LANE_GROUP_KNOBS.items() for kn in knobs]
 
 
 def gv_spec(name):
