@@ -33,6 +33,8 @@ int kinematic_has_step_kinds(void);
 int kinematic_batch_predict_update_kinds(double *x, double *P, const double *Q, const double *dt_vec, double dt, const int32_t *kinds, double *z, const double *R, int r_per_filter, int64_t n, int norm_quats, uint8_t *flags, const uint8_t *active, void *stream);
 int kinematic_batch_update_kinds(double *x, double *P, const int32_t *kinds, double *z, const double *R, int r_per_filter, int64_t n, int norm_quats, uint8_t *flags, const uint8_t *active, void *stream);
 int kinematic_batch_timeline_push_kinds(const double *t, const uint8_t *act, double *ft, const double *x, const double *P, int64_t n, int64_t K, int64_t nmax, double *ring_t, double *ring_x, double *ring_P, int32_t *ring_kind, int32_t *ring_nobs, double *ring_z, double *ring_R, double *ring_ea, int64_t *ring_head, int64_t *ring_length, const int32_t *kinds, const double *z_obs, const double *R, int r_per_filter, void *stream);
+int kinematic_batch_rewind_locate(const uint8_t *late, const double *t, int64_t n, int64_t K, double *ring_t, double *ring_x, double *ring_P, int64_t *ring_head, int64_t *ring_length, double max_rewind_age, double *x, double *P, double *ft, double *dt_out, uint8_t *act_out, int32_t *rep_slot, int32_t *rep_n, uint8_t *drop_out, int32_t *counts, void *stream);
+int kinematic_batch_rewind_fetch(const int32_t *rep_slot, const int32_t *rep_n, int64_t q, const double *t_prev, int64_t n, int64_t K, int64_t nmax, double *ring_t, int32_t *ring_kind, double *ring_z, double *ring_R, double *t_out, double *dt_out, int32_t *kinds_out, uint8_t *act_out, double *z_out, double *z_keep, double *R_out, void *stream);
 int kinematic_batch_maha_1(const double *x, const double *P, const double *z, const double *R, int r_per_filter, const double *ea, int64_t n, double *d2, void *stream);
 void kinematic_msckf_dims(int *dims);
 int kinematic_kind_eadim(int kind);

@@ -292,7 +292,47 @@ extern "C" {
                                              const double *z_obs, const double *R, int r_per_filter,              \
                                              void *stream);
 
-#define RN_DECLARE_BATCH_KIND_MASKED(name, k)                                                                   \
+/* Per-filter timelines, THE LATE OBSERVATION ON THE DEVICE: the rewind of every filter batch_timeline_plan found late, each in its own ring
+ * (EKF_sym.rewind and the too-old test in front of it, the reference's ekf_sym.py:418-438, 464-471), and the gather of the
+ * overtaken entries, one replay position of all rewound filters at a time, into the buffers batch_predict_update_kinds and
+ * batch_timeline_push_kinds take (the fast-forward, ekf_sym.py:477-479).  DEVICE pointers, asynchronous on `stream`, status codes as in
+ * section 2; n == 0 is a no-op.  Ring layout as in batch_timeline_push; K >= 1.
+ *
+ * batch_rewind_locate.  late / dt_out / act_out (n) are the plan's buffers; x, P, ft the filters' state and times; rep_slot / rep_n (n) int32,
+ * drop_out (n) bytes; counts: two int32, ZEROED by the caller on the stream before the call.  With L = ring_length[i] and H = ring_head[i]
+ * (both clamped: 0 <= H < K, 0 <= L <= K) and T[j] = ring_t[((H + j) % K) * n + i], j < L, per filter i:
+ *   late[i] == 0                                      drop_out = 0, rep_n = 0, nothing else of the filter is touched
+ *   L == 0, t < T[0] or t < T[L-1] - max_rewind_age   too old: drop_out = 1, rep_n = 0, counts[1] += 1 (a vector atomic); nothing else changes
+ *                                                     (the plan left act_out = 0, dt_out = 0: the filter sits this call out)
+ *   otherwise, ix = #{j < L: T[j] <= t}               (bisect_right; 1 <= ix <= L) x[i], P[i] <- entry (H + ix - 1) % K; ft = T[ix-1];
+ *                                                     dt_out = t - T[ix-1]; act_out = 1; rep_slot = (H + ix) % K; rep_n = L - ix;
+ *                                                     ring_length = ix; drop_out = 0; counts[0] = max(counts[0], rep_n) (a vector atomic)
+ * batch_rewind_fetch, replay position q >= 0.  Per filter i with rep_n[i] > q, e = ((rep_slot[i] + q) % K) * n + i: t_out = ring_t[e];
+ * dt_out = t_out - t_prev[i]; kinds_out = ring_kind[e]; act_out = 1, or 0 where that is not a kind of the model; the entry's FIRST observation
+ * row (zmax doubles) to z_out (n, zmax) and again to z_keep (n, zmax) -- the step overwrites z_out with the residual, the checkpoint wants the
+ * observation --; its noise, zmax x zmax in the ring, compacted to the leading Z * Z doubles (row-major) of row i of R_out (n, zmax * zmax):
+ * r_per_filter != 0 of batch_predict_update_kinds.  Every other filter: act_out = 0, dt_out = 0, kinds_out = 0, t_out = t_prev[i], its z and
+ * R rows untouched.  t_prev is the call's own t for q == 0 and the previous fetch's t_out after that -- never ft, which the push of the
+ * position before may not have written yet.
+ *
+ * ORDER of a late call on the one stream: plan -> locate -> fetch(0) -> the call's own step (the plan's dt / act: rewound and in-order filters
+ * together) -> its push -> for q = 0 .. counts[0] - 1: fetch(q + 1) into a second buffer set, batch_predict_update_kinds and
+ * batch_timeline_push_kinds on the current set.  Every entry is fetched before a launch overwrites its slot: the call's own push writes the
+ * slot of replay position 0, the push behind position q the slot of position q + 1.  A push evicts only on a full ring -- here the last
+ * replay's push at most, and it takes the filter's oldest entry, never a replay entry (ix >= 1). */
+#define RN_DECLARE_BATCH_REWIND(name)                                                                            \
+  int RN_FN(name, batch_rewind_locate)(const uint8_t *late, const double *t, int64_t n, int64_t K, double *ring_t, \
+                                       double *ring_x, double *ring_P, int64_t *ring_head, int64_t *ring_length,  \
+                                       double max_rewind_age, double *x, double *P, double *ft, double *dt_out,   \
+                                       uint8_t *act_out, int32_t *rep_slot, int32_t *rep_n, uint8_t *drop_out,    \
+                                       int32_t *counts, void *stream);                                            \
+  int RN_FN(name, batch_rewind_fetch)(const int32_t *rep_slot, const int32_t *rep_n, int64_t q,                   \
+                                      const double *t_prev, int64_t n, int64_t K, int64_t nmax, double *ring_t,   \
+                                      int32_t *ring_kind, double *ring_z, double *ring_R, double *t_out,          \
+                                      double *dt_out, int32_t *kinds_out, uint8_t *act_out, double *z_out,        \
+                                      double *z_keep, double *R_out, void *stream);
+
+#define RN_DECLARE_BATCH_KIND_MASKED(name, k)                                                                  \
   int RN_FN(name, batch_update_##k##_masked)(double *x, double *P, double *z, const double *R, int r_per_filter,  \
                                              const double *ea, int64_t n, int norm_quats, uint8_t *flags,         \
                                              const uint8_t *active, void *stream);                                \

@@ -430,6 +430,30 @@ def _abi_batched(spec, s):
   RN_HIP(hipGetLastError());
   return rn::OK;""" if s.has_kinds else no_kinds)
 
+  # The late observation of per-filter timelines on the device (rn::k_rewind_locate / k_rewind_fetch, include/rednose_amd_filter.h): the rewind of
+  # every late filter in its own ring, then one replay position of all rewound filters gathered into the buffers of the mixed-kind step
+  rw_ring = "rn::RewindRing{{K, {nmax}, ring_t, {x}, {P}, {kind}, {z}, {R}, {head}, {length}}}"
+  a.fn("int", "batch_rewind_locate", "const uint8_t *late, const double *t, int64_t n, int64_t K, double *ring_t, double *ring_x, double *ring_P, "
+       "int64_t *ring_head, int64_t *ring_length, double max_rewind_age, double *x, double *P, double *ft, double *dt_out, uint8_t *act_out, "
+       "int32_t *rep_slot, int32_t *rep_n, uint8_t *drop_out, int32_t *counts, void *stream",
+       _batched("n >= 0 && K >= 1 && late && t && ring_t && ring_x && ring_P && ring_head && ring_length", [],
+                require2="x && P && ft && dt_out && act_out && rep_slot && rep_n && drop_out && counts",
+                launch=f"""  hipLaunchKernelGGL(rn::k_rewind_locate, {GRID_PUSH},
+                     late, t, n, {sizes}, {rw_ring.format(nmax=1, x="ring_x", P="ring_P", kind="nullptr", z="nullptr", R="nullptr", head="ring_head", length="ring_length")}, max_rewind_age,
+                     x, P, ft, dt_out, act_out, rep_slot, rep_n, drop_out, counts);"""))
+  if len(spec.kinds) <= KINDS_MAX:
+    fetch = f"""  const rn::TimelineKinds tk{{nullptr, {len(spec.kinds)}, {{{tab}}}}};
+  hipLaunchKernelGGL(rn::k_rewind_fetch, {GRID_PUSH},
+                     rep_slot, rep_n, q, t_prev, n, {rw_ring.format(nmax="nmax", x="nullptr", P="nullptr", kind="ring_kind", z="ring_z", R="ring_R", head="nullptr", length="nullptr")}, {zmax}, tk,
+                     t_out, dt_out, kinds_out, act_out, z_out, z_keep, R_out);"""
+  else:
+    fetch = _unsupported(f"batch_rewind_fetch: the model has more than {KINDS_MAX} kinds", unused="(void)stream; ")
+  a.fn("int", "batch_rewind_fetch", "const int32_t *rep_slot, const int32_t *rep_n, int64_t q, const double *t_prev, int64_t n, int64_t K, int64_t nmax, "
+       "double *ring_t, int32_t *ring_kind, double *ring_z, double *ring_R, double *t_out, double *dt_out, int32_t *kinds_out, uint8_t *act_out, "
+       "double *z_out, double *z_keep, double *R_out, void *stream",
+       _batched("n >= 0 && K >= 1 && nmax >= 1 && q >= 0 && rep_slot && rep_n && t_prev && ring_t && ring_kind && ring_z && ring_R", [],
+                require2="t_out && dt_out && kinds_out && act_out && z_out && z_keep && R_out", launch=fetch, hip_check=len(spec.kinds) <= KINDS_MAX))
+
   for k in spec.kinds:
     a.fn("int", f"batch_maha_{k.kind}", "const double *x, const double *P, const double *z, const double *R, int r_per_filter, const double *ea, int64_t n, double *d2, void *stream",
          _batched(f"n >= 0 && x && P && z && R && d2{ea_req(k)}", ["x", "P", "z", "R"], s.step.launch_maha(k.kind)))

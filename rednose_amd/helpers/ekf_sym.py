@@ -423,6 +423,12 @@ class BatchedEKF:
       the library exports {name}_batch_timeline_plan / _push, False = never, True = required, KalmanError otherwise): filter times
       and rings stay in HBM, the host reads one integer per call; `filter_time` is then the (N,) tensor the checkpoint kernel writes
       in place.  A call with a late filter takes the torch path on the same rings.  pf_stats counts the calls of either path.
+      device_rewind=True (opt-in; needs the device timeline, {name}_batch_rewind_locate / _fetch and {name}_has_step_kinds() == 1,
+      KalmanError otherwise) serves the late call on the device too: the rewind of every late filter in one launch, two integers read
+      back, then per overtaken ring position one fetch, one mixed-kind step and one push.  Still on the torch path: ring entries or calls
+      with several observations per filter, keep_estimate, libraries without the mixed-kind kernel (and the C++ orchestrator
+      EKFSymBatch has no device rewind).  rewind_stats counts the late calls by the path that served them; one served on the device
+      also counts as pf_stats["fast"].
 
   Compute goes through the generated library's `{name}_batch_*` entry points on the current torch HIP
   stream; torch is used only for device memory and streams.  No GPU / no library => KalmanError.
@@ -431,7 +437,8 @@ class BatchedEKF:
 
   def __init__(self, folder, name, Q, x_initial, P_initial, dim_main, dim_main_err,  # pylint: disable=dangerous-default-value
                N=0, dim_augment=0, dim_augment_err=0, maha_test_kinds=[], quaternion_idxs=[], global_vars=None,
-               max_rewind_age=1.0, logger=logging, batch=1, device=None, rewind_to_keep=0, per_filter=False, device_timeline=None):
+               max_rewind_age=1.0, logger=logging, batch=1, device=None, rewind_to_keep=0, per_filter=False, device_timeline=None,
+               device_rewind=False):
     import torch  # pylint: disable=import-outside-toplevel
     if not torch.cuda.is_available():
       raise KalmanError("BatchedEKF needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
@@ -488,6 +495,13 @@ class BatchedEKF:
     self.pf_stats = {"fast": 0, "legacy": 0}      # per-filter calls served by the device timeline / by the torch bookkeeping (late observations: rewind)
     self._ft_dev = None                # the (N,) tensor of filter times k_timeline_push writes in place (== self.filter_time while it is current)
     self._tl = None                    # buffers of the device timeline (_timeline_buffers)
+    # The late call on the device as well (opt-in): {name}_batch_rewind_locate / _fetch and the mixed-kind step replay the overtaken entries.
+    self._device_rewind = bool(device_rewind)
+    if self._device_rewind and not (self._device_timeline and self._has_rewind_abi() and self._has_step_kinds()):
+      raise KalmanError(f"device_rewind=True needs the device timeline, {name}_batch_rewind_locate / _fetch and the mixed-kind step kernel "
+                        f"({name}_has_step_kinds() == 1): lib{name}.so lacks one of them")
+    self.rewind_stats = {"device": 0, "torch": 0}      # calls with a late filter, by the path that served them
+    self._rw = None                    # buffers of the device rewind (_rewind_buffers)
 
     self.Q = torch.as_tensor(np.ascontiguousarray(Q, dtype=np.float64), device=self.device)
     self._R_cache = OrderedDict()          # small LRU of shared (Z, Z) noise matrices already on the device
@@ -511,6 +525,9 @@ class BatchedEKF:
 
   def _has_timeline_abi(self):
     return all(hasattr(self._lib, f"{self.name}_batch_timeline_{s}") for s in ("plan", "push"))
+
+  def _has_rewind_abi(self):
+    return all(hasattr(self._lib, f"{self.name}_batch_rewind_{s}") for s in ("locate", "fetch"))
 
   def _dev(self, a, shape=None):
     torch = self._torch
@@ -899,6 +916,7 @@ class BatchedEKF:
     if bool(late.any()):                   # (the one host round trip of an in-order call: whether any filter has to rewind decides what is launched)
       if self.rewind_to_keep <= 0:
         raise AssertionError("observation older than a filter's time (enable rewind_to_keep to reorder late observations)")
+      self.rewind_stats["torch"] += 1
       dropped, replay = self._ring_rewind(late, tt)
       any_dropped = bool(dropped.any())
       if any_dropped:
@@ -1009,7 +1027,7 @@ class BatchedEKF:
     # the per-kind path: a filter is late, or the library has no mixed-kind kernel
     self.pf_stats["legacy"] += 1
     fl = torch.full((N,), 16, dtype=torch.uint8, device=self.device)
-    stats = dict(self.pf_stats)
+    stats, rw_stats = dict(self.pf_stats), dict(self.rewind_stats)
     for k in present:
       Z, m = self.zdims[k], has & (kd == k)
       zk = zt[:, :Z].contiguous()
@@ -1020,6 +1038,9 @@ class BatchedEKF:
       zt[:, :Z] = torch.where(m[:, None], y, zt[:, :Z])
       fl = torch.where(m, self.flags, fl)
     self.pf_stats = stats
+    if sum(self.rewind_stats.values()) > sum(rw_stats.values()):      # one late call, however many per-kind calls served it
+      rw_stats["torch"] += 1
+    self.rewind_stats = rw_stats
     self.flags.copy_(fl)
     return zt
 
@@ -1047,8 +1068,11 @@ class BatchedEKF:
     count = int(b["host_np"][0])
     late, b["seen"] = count != b["seen"], count
     self._keepalive_timeline = (tt, a8, kd, zt, Rd)
+    rewound = None
     if late:
-      return None
+      if not self._rewind_on_device(True, False):
+        return None
+      rewound = self._rewind_locate(tt, ft, b)
     self._call("batch_predict_update_kinds", self._p(self.x), self._p(self.P), self._p(self.Q), self._p(b["dt"]), 0.0, self._p(kd), self._p(zt), self._p(Rd), per,
                N, self.norm_quats, self._p(self.flags), self._p(b["act"]), self._stream())
     if K > 0:
@@ -1061,6 +1085,8 @@ class BatchedEKF:
     else:
       self._call("batch_timeline_push_kinds", self._p(tt), self._p(b["act"]), self._p(ft), None, None, N, 0, 0, None, None, None, None, None, None, None, None,
                  None, None, self._p(kd), None, None, 0, self._stream())
+    if rewound is not None:
+      self._rewind_replay(*rewound)
     return zt
 
   # -- the in-order call with its bookkeeping on the device ----------------------------------------------------------
@@ -1115,9 +1141,12 @@ class BatchedEKF:
     torch.cuda.current_stream(self.device).synchronize()
     count = int(b["host_np"][0])
     late, b["seen"] = count != b["seen"], count        # (the counter accumulates)
+    rewound = None
     if late:
-      self._keepalive_timeline = (tt, a8)
-      return None
+      if not self._rewind_on_device(not multi, keep_estimate):
+        self._keepalive_timeline = (tt, a8)
+        return None
+      rewound = self._rewind_locate(tt, ft, b)
     z_obs = None
     if copy_z:
       z_keep, z_sf, z_so = b["z_keep"], Z, 0
@@ -1137,6 +1166,8 @@ class BatchedEKF:
                  self._p(r["head"]), self._p(r["length"]), int(kind), n, self._p(z_keep), z_sf, z_so, self._p(Rk), per, Z * Z, r_so,
                  self._p(eak), EA, ea_so, self._stream())
       self._keepalive_timeline = (tt, a8, z_keep, Rk, eak)
+      if rewound is not None:
+        self._rewind_replay(*rewound)
     else:
       self._call("batch_timeline_push", self._p(tt), self._p(b["act"]), self._p(ft), None, None, N, 0, 0, None, None, None, None, None, None, None, None,
                  None, None, int(kind), n, None, 0, 0, None, 0, 0, 0, None, 0, 0, self._stream())
@@ -1147,6 +1178,82 @@ class BatchedEKF:
     if multi:
       return ((est[0], xk_k, est[1], Pk_k, tt, kind, list(torch.stack(zl, 1).unbind(1)), torch.stack(z_obs, 1), extra_args),)
     return ((est[0], xk_k, est[1], Pk_k, tt, kind, zl[0], z_obs[0], extra_args),)
+
+  # -- the late call on the device (device_rewind=True) ----------------------------------------------------------------
+  def _rewind_on_device(self, single, keep_estimate):
+    """Does the device serve this late call?  One observation per filter in the call and in every ring entry (the replay is one mixed-kind
+    step per position), no Estimate wanted.  Anything else: the torch path, on the same rings."""
+    return (self._device_rewind and self.rewind_to_keep > 0 and single and not keep_estimate and
+            (self._ring is None or self._ring["nmax"] == 1))
+
+  def _rewind_buffers(self):
+    """What batch_rewind_locate writes and the two buffer sets batch_rewind_fetch fills in turn, allocated once per object (and stream): every
+    launch that reads them is on this stream, in front of the next call's."""
+    torch = self._torch
+    N, zmax, stream = self.batch, max(self.zdims.values()), self._torch.cuda.current_stream(self.device).cuda_stream
+    w = self._rw
+    if w is None or w["stream"] != stream:
+      f64, dev = dict(dtype=torch.float64, device=self.device), self.device
+
+      def bufset():
+        return dict(t=torch.zeros(N, **f64), dt=torch.zeros(N, **f64), kinds=torch.zeros(N, dtype=torch.int32, device=dev),
+                    act=torch.zeros(N, dtype=torch.uint8, device=dev), z=torch.zeros((N, zmax), **f64), z_keep=torch.zeros((N, zmax), **f64),
+                    R=torch.zeros((N, zmax * zmax), **f64))
+      w = self._rw = dict(stream=stream, slot=torch.zeros(N, dtype=torch.int32, device=dev), n=torch.zeros(N, dtype=torch.int32, device=dev),
+                          drop=torch.zeros(N, dtype=torch.uint8, device=dev), counts=torch.zeros(2, dtype=torch.int32, device=dev),
+                          host=torch.zeros(2, dtype=torch.int32).pin_memory(), flags=torch.zeros(N, dtype=torch.uint8, device=dev),
+                          sets=(bufset(), bufset()))
+      w["host_np"] = w["host"].numpy()
+    return w
+
+  def _rewind_fetch(self, q, t_prev, dst):
+    r, w = self._ring, self._rw
+    self._call("batch_rewind_fetch", self._p(w["slot"]), self._p(w["n"]), q, self._p(t_prev), self.batch, self.rewind_to_keep, r["nmax"],
+               self._p(r["t"]), self._p(r["kind"]), self._p(r["z"]), self._p(r["R"]), self._p(dst["t"]), self._p(dst["dt"]), self._p(dst["kinds"]),
+               self._p(dst["act"]), self._p(dst["z"]), self._p(dst["z_keep"]), self._p(dst["R"]), self._stream())
+
+  def _rewind_locate(self, tt, ft, b):
+    """The rewind of the filters the plan found late (batch_rewind_locate on the plan's buffers `b`: a rewound filter steps in this call
+    after all, from its checkpoint), the call's second and last host round trip -- how many positions to replay, how many filters
+    were too old -- and the fetch of replay position 0, which the call's own push is about to overwrite.  -> (positions, dropped)."""
+    torch = self._torch
+    if self._ring is None:
+      self._ring_alloc(1)
+    r, w = self._ring, self._rewind_buffers()
+    w["counts"].zero_()
+    self._call("batch_rewind_locate", self._p(b["late"]), self._p(tt), self.batch, self.rewind_to_keep, self._p(r["t"]), self._p(r["x"]), self._p(r["P"]),
+               self._p(r["head"]), self._p(r["length"]), float(self.max_rewind_age), self._p(self.x), self._p(self.P), self._p(ft), self._p(b["dt"]),
+               self._p(b["act"]), self._p(w["slot"]), self._p(w["n"]), self._p(w["drop"]), self._p(w["counts"]), self._stream())
+    w["host"].copy_(w["counts"], non_blocking=True)
+    torch.cuda.current_stream(self.device).synchronize()
+    positions, dropped = int(w["host_np"][0]), int(w["host_np"][1])
+    if dropped > 0:
+      self.logger.error(f"observation too old for {dropped} filter(s) of the batch, ignoring it for them")
+    if positions > 0:
+      self._rewind_fetch(0, tt, w["sets"][0])
+    self.rewind_stats["device"] += 1
+    return positions, dropped
+
+  def _rewind_replay(self, positions, dropped):
+    """Behind the call's own step and push: flag 48 for the filters that were too old, then the fast-forward -- per replay position one
+    fetch (of the NEXT position), one mixed-kind step and one push, whatever kinds the overtaken entries hold.  The step's flags go to a
+    scratch buffer: the flags the caller reads are this call's."""
+    N, K, r, w = self.batch, self.rewind_to_keep, self._ring, self._rw
+    ft = self._ft_dev
+    if dropped > 0:
+      self._call("batch_flags_set", self._p(self.flags), self._p(w["drop"]), 48, N, self._stream())
+    # Every entry is fetched before a launch overwrites its slot: the call's own push wrote the slot of replay position 0 (fetched by
+    # _rewind_locate), the push behind position q writes the slot of position q + 1 (fetched in front of step q).  A push evicts only on a
+    # full ring -- the last replay's push at most -- and takes the filter's oldest entry, never a replay entry (the rewind keeps >= 1).
+    for q in range(positions):
+      cur, nxt = w["sets"][q & 1], w["sets"][(q + 1) & 1]
+      if q + 1 < positions:
+        self._rewind_fetch(q + 1, cur["t"], nxt)      # (t_prev: this position's times, not ft -- its push has not run yet)
+      self._call("batch_predict_update_kinds", self._p(self.x), self._p(self.P), self._p(self.Q), self._p(cur["dt"]), 0.0, self._p(cur["kinds"]),
+                 self._p(cur["z"]), self._p(cur["R"]), 1, N, self.norm_quats, self._p(w["flags"]), self._p(cur["act"]), self._stream())
+      self._call("batch_timeline_push_kinds", self._p(cur["t"]), self._p(cur["act"]), self._p(ft), self._p(self.x), self._p(self.P), N, K, r["nmax"],
+                 self._p(r["t"]), self._p(r["x"]), self._p(r["P"]), self._p(r["kind"]), self._p(r["nobs"]), self._p(r["z"]), self._p(r["R"]), self._p(r["ea"]),
+                 self._p(r["head"]), self._p(r["length"]), self._p(cur["kinds"]), self._p(cur["z_keep"]), self._p(cur["R"]), 1, self._stream())
 
   def _ring_alloc(self, nmax=1):
     """Per-filter checkpoint rings in HBM: K entries per filter, an entry = time, state after the call, and the call's observation(s) --

@@ -931,6 +931,131 @@ __global__ __launch_bounds__(256) void k_timeline_push(const double* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------
+// per-filter timelines, the late observation on the device: k_rewind_locate is EKF_sym.rewind (ekf_sym.py:418-438, 464-471) for every filter the
+// plan found late, each in its own ring; k_rewind_fetch gathers one position of the overtaken entries of all rewound filters into the buffers
+// of the mixed-kind step, which with k_timeline_push replays it (the fast-forward, ekf_sym.py:477-479).  Between the two the orchestrator
+// reads two integers.  One wavefront per filter, four per workgroup, grid-stride, like k_timeline_push.
+// ------------------------------------------------------------------------------------------------
+// The parts of the rings the two kernels look into (layout: TimelineRing)
+struct RewindRing {
+  int64_t K, nmax;
+  const double *t, *x, *P;
+  const int32_t* kind;
+  const double *z, *R;
+  const int64_t* head;
+  int64_t* length;
+};
+
+// With L = length[f], H = head[f], T[j] = ring t of entry (H + j) % K, for the filters with late[f] != 0:
+//   L == 0, t < T[0] or t < T[L-1] - max_rewind_age: too old -- drop_out = 1, rep_n = 0, counts[1] += 1, nothing else of the filter changes
+//   otherwise, ix = #{j < L: T[j] <= t} (bisect_right; >= 1): x, P <- entry ix - 1, ft = T[ix-1], dt_out = t - ft, act_out = 1 (the filter
+//   steps in this call after all), rep_slot = (H + ix) % K, rep_n = L - ix (the entries to replay), length = ix, counts[0] = max(., rep_n)
+// Filters that are not late: drop_out = 0, rep_n = 0.  counts (2 x int32): zeroed by the caller.
+__global__ __launch_bounds__(256) void k_rewind_locate(const uint8_t* __restrict__ late, const double* __restrict__ t, const int64_t n, const int D,
+                                                       const int EE, const RewindRing r, const double max_rewind_age, double* __restrict__ x,
+                                                       double* __restrict__ P, double* __restrict__ ft, double* __restrict__ dt_out,
+                                                       uint8_t* __restrict__ act_out, int32_t* __restrict__ rep_slot, int32_t* __restrict__ rep_n,
+                                                       uint8_t* __restrict__ drop_out, int32_t* __restrict__ counts) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  for (int64_t f = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); f < n; f += (int64_t)gridDim.x * 4) {
+    if (late[f] == 0) {
+      if (lane == 0) {
+        drop_out[f] = 0;
+        rep_n[f] = 0;
+      }
+      continue;
+    }
+    int64_t H = r.head[f], L = r.length[f];
+    if (H < 0 || H >= r.K) H = 0;                          // (a ring position is never trusted as an address)
+    if (L < 0) L = 0;
+    if (L > r.K) L = r.K;
+    const double tf = t[f];
+    bool too_old = L == 0;
+    if (!too_old) {
+      const double oldest = r.t[(H % r.K) * n + f], newest = r.t[((H + L - 1) % r.K) * n + f];
+      too_old = tf < oldest || tf < newest - max_rewind_age;
+    }
+    if (too_old) {
+      if (lane == 0) {
+        drop_out[f] = 1;
+        rep_n[f] = 0;
+        atomicAdd(counts + 1, 1);
+      }
+      continue;
+    }
+    int64_t ix = 0;                                         // (every lane of the wavefront takes part in the ballot: the bound is uniform)
+    for (int64_t base = 0; base < L; base += WAVE) {
+      const int64_t j = base + lane;
+      const bool le = j < L && r.t[((H + j) % r.K) * n + f] <= tf;
+      ix += __popcll(__ballot(le));
+    }
+    if (ix < 1) ix = 1;                                     // (t >= T[0] held above)
+    const int64_t e = ((H + ix - 1) % r.K) * n + f;
+    const double te = r.t[e];
+    wave_copy(x + f * D, r.x + e * D, D, lane);
+    wave_copy(P + f * EE, r.P + e * EE, EE, lane);
+    if (lane == 0) {
+      ft[f] = te;
+      dt_out[f] = tf - te;
+      act_out[f] = 1;
+      rep_slot[f] = (int32_t)((H + ix) % r.K);
+      rep_n[f] = (int32_t)(L - ix);
+      r.length[f] = ix;
+      drop_out[f] = 0;
+      if (L > ix) atomicMax(counts, (int32_t)(L - ix));
+    }
+  }
+}
+
+// Replay position q of every rewound filter (rep_n[f] > q), entry e = (rep_slot[f] + q) % K of its ring, into what batch_predict_update_kinds
+// and batch_timeline_push_kinds take: t_out = the entry's time, dt_out = t_out - t_prev, kinds_out, act_out = 1 (0: not a kind of the table),
+// its first observation (zmax doubles) in z_out and again in z_keep -- the step overwrites z_out with the residual --, its noise compacted
+// from zmax x zmax to the leading Z * Z doubles of the row of R_out.  Other filters: act_out = 0, dt_out = 0, kinds_out = 0, t_out = t_prev.
+// t_prev: the call's t for q == 0, the previous fetch's t_out after that (never ft: the push that writes it may not have run yet).
+__global__ __launch_bounds__(256) void k_rewind_fetch(const int32_t* __restrict__ rep_slot, const int32_t* __restrict__ rep_n, const int64_t q,
+                                                      const double* __restrict__ t_prev, const int64_t n, const RewindRing r, const int zmax,
+                                                      const TimelineKinds tk, double* __restrict__ t_out, double* __restrict__ dt_out,
+                                                      int32_t* __restrict__ kinds_out, uint8_t* __restrict__ act_out, double* __restrict__ z_out,
+                                                      double* __restrict__ z_keep, double* __restrict__ R_out) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  for (int64_t f = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); f < n; f += (int64_t)gridDim.x * 4) {
+    const double tp = t_prev[f];
+    int64_t slot = rep_slot[f];
+    if (rep_n[f] <= q || slot < 0) {                        // (also a negative slot: never an address)
+      if (lane == 0) {
+        t_out[f] = tp;
+        dt_out[f] = 0.0;
+        kinds_out[f] = 0;
+        act_out[f] = 0;
+      }
+      continue;
+    }
+    const int64_t e = ((slot % r.K + q % r.K) % r.K) * n + f;
+    const int kind_f = r.kind[e];
+    int Zf = 0;
+    for (int i = 0; i < tk.count; i++) if (tk.tab[i].kind == kind_f) Zf = tk.tab[i].Z;
+    if (lane == 0) {
+      const double te = r.t[e];
+      t_out[f] = te;
+      dt_out[f] = te - tp;
+      kinds_out[f] = kind_f;
+      act_out[f] = (uint8_t)(Zf > 0);
+    }
+    const double* rz = r.z + e * r.nmax * zmax;
+    const double* rR = r.R + e * r.nmax * zmax * zmax;
+    for (int i = lane; i < zmax; i += WAVE) {
+      const double v = rz[i];
+      z_out[f * zmax + i] = v;
+      z_keep[f * zmax + i] = v;
+    }
+    for (int i = lane; i < Zf * Zf; i += WAVE) {
+      const int row = i / Zf, c = i - row * Zf;
+      R_out[f * zmax * zmax + i] = rR[row * zmax + c];
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // host-side staging for the single-filter host-pointer entry points (the reference's scalar ABI)
 // ------------------------------------------------------------------------------------------------
 // One buffer of PINNED host memory mapped into the device's address space: an entry point packs its arguments into `host` with memcpy,

@@ -1,11 +1,14 @@
 """Per-call wall time of per-filter timelines (BatchedEKF(per_filter=True)) on kinematic6 with the in-order bookkeeping on the device (the
 default where the library has {name}_batch_timeline_plan / _push) against the torch bookkeeping (device_timeline=False), in ONE process:
 4 096 and 65 536 filters, every filter on its own clock, without a ring and with a ring of 8; in order, and with 1 % of the filters late
-in every call (such a call takes the torch path on either object).  The two objects are fed the same calls in alternating blocks of CALLS
-calls; a block is timed with the host clock around calls that end in a device synchronise.  Per row: min / median / max over REPS blocks
-and the verdict against the spread (max - min) of the torch rows.
+in every call.  Such a call takes the torch path on either object; the 1 % late rows time a third object, device_rewind=True, which serves it
+on the device (batch_rewind_locate / _fetch, one mixed-kind step and one push per replay position).  The objects are fed the same calls in
+alternating blocks of CALLS calls; a block is timed with the host clock around calls that end in a device synchronise.  Per row: min / median /
+max over REPS blocks and the verdict against the spread (max - min) of the torch rows.
 
-  python tools/pf_device_timeline_time.py [--out FILE]
+  python tools/pf_device_timeline_time.py [--out FILE] [--late-only]
+
+--late-only: the 1 % late rows alone (profiles/pf_device_rewind_call_times.txt).
 """
 import argparse
 import os
@@ -24,6 +27,7 @@ CALLS, REPS, WARM = 200, 7, 50
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=None)
+ap.add_argument("--late-only", action="store_true")
 args = ap.parse_args()
 lines = []
 
@@ -71,13 +75,19 @@ def stats(v):
 
 say(f"# per-filter timelines, kinematic6, us per call: min / median / max of {REPS} blocks of {CALLS} calls after {WARM} warm-up calls,")
 say("# the objects alternating block by block in one process.  torch = device_timeline=False (the bookkeeping in torch operations),")
-say("# device = the default (batch_timeline_plan, the step, batch_timeline_push).  spread = max - min of the torch row.")
-say("# verdict, in-order rows: LOWER when median(device) < median(torch) - spread.  1 % late rows: NOT SLOWER when median(device) <= median(torch) + spread.")
+say("# device = the default (batch_timeline_plan, the step, batch_timeline_push; a call with a late filter: the torch path),")
+say("# device rewind = device_rewind=True (a call with a late filter: batch_rewind_locate / _fetch, mixed-kind replay).  spread = max - min of the torch row.")
+say("# verdict, in-order rows: LOWER when median(device) < median(torch) - spread.  1 % late rows: NOT SLOWER when median(device) <= median(torch) + spread;")
+say("# device rewind: LOWER when median(device rewind) < median(torch) - spread.")
 say(f"# {torch.cuda.get_device_name(0)}, torch {torch.__version__}")
 for n in (4096, 65536):
   for ring in (0, 8):
     for late in ((False, True) if ring else (False,)):
+      if args.late_only and not late:
+        continue
       variants = [("torch", dict(device_timeline=False), {}), ("device", {}, {})]
+      if late:
+        variants.append(("device rewind", dict(device_rewind=True), {}))
       if ring and not late:
         variants.append(("device, z cloned", {}, dict(timeline_plan_copies_z=False)))      # the observation kept by a clone() instead of by the plan kernel
       runs = []
@@ -98,13 +108,16 @@ for n in (4096, 65536):
         lo, med, hi = stats(v)
         verdict = ""
         if label != "torch":
-          if late:
+          if label == "device rewind":
+            verdict = "LOWER" if med < med0 - (hi0 - lo0) else "NOT LOWER"
+          elif late:
             verdict = "NOT SLOWER" if med <= med0 + (hi0 - lo0) else "SLOWER"
           else:
             verdict = "LOWER" if med < med0 - (hi0 - lo0) else "NOT LOWER"
           verdict = f"   {verdict} ({med0 / med:.2f} x, spread {hi0 - lo0:.1f})"
-        st = s.f.pf_stats
-        say(f"{what:42s} {label:18s} {lo:8.1f} / {med:8.1f} / {hi:8.1f}   fast {st['fast']:5d} torch {st['legacy']:5d}{verdict}")
+        st, rw = s.f.pf_stats, s.f.rewind_stats
+        served = f"   late calls: device {rw['device']:5d} torch {rw['torch']:5d}" if late else ""
+        say(f"{what:42s} {label:18s} {lo:8.1f} / {med:8.1f} / {hi:8.1f}   fast {st['fast']:5d} torch {st['legacy']:5d}{served}{verdict}")
 if args.out:
   with open(args.out, "w", encoding="utf-8") as f:
     f.write("\n".join(lines) + "\n")
