@@ -292,6 +292,29 @@ extern "C" {
                                              const double *z_obs, const double *R, int r_per_filter,              \
                                              void *stream);
 
+/* THE FUSED RUN WITH A SCHEDULE PER FILTER: N recorded logs replayed in ONE launch.  batch_run keeps x and P on chip for T steps but shares
+ * its schedule among the filters; batch_predict_update_kinds gives every filter its own kind and dt but moves the whole state through HBM at
+ * every tick.  Here filter i walks its own column of kinds (T, n) int32 and dts (T, n) with x and P resident in registers.
+ *   {name}_has_batch_run_pf() == 1: the library has the kernel (both kernel families, up to 64 error states).  0: MSCKF models, models
+ *   with a kind that takes extra arguments, models without batch_run, or a kernel that did not fit the register file -- batch_run_pf then
+ *   returns status 4 and nothing is launched (walk the schedule with batch_predict_update_kinds).
+ * All pointers are DEVICE pointers; alignment rules, status codes and argument checks are those of batch_run; T == 0 or n == 0 is a no-op
+ * that returns 0.  z (T, n, zmax) in: z, out: y; R is the per-kind table of batch_predict_update_kinds with r_per_filter == 0: (num_kinds,
+ * zmax * zmax), one row per kind in the order of {name}_kinds(), the leading Z * Z entries of a row are that kind's row-major R.  flags
+ * (T, n), trace_x (T, n, D), trace_P (T, n, E, E) may be NULL.  Per entry (t, i):
+ *   kinds[t, i] <= 0 (idle)   filter i is not touched at step t, no predict; dts[t, i] is ignored; the z row passes through bit for bit; flag 16
+ *   a kind of the model       predict(dts[t, i]), renormalisation as in batch_run, then the update of that kind: the first Z entries of the z row
+ *                             become the residual, the rest of the row passes through; flags as in batch_run, the gate bit included
+ *   any other value           untouched like an idle entry, flag 8 (the rule of batch_predict_update_kinds, not batch_run's "predict, then flag 8")
+ * trace_x / trace_P row (t, i) is filter i's pair after step t -- for an idle or flag-8 entry the pair it had: the trace is dense.  The
+ * covariance is read as (P + P^T) / 2 as the state enters the registers, like batch_run (see "Asymmetric covariances" above).  A filter
+ * without a stepped entry in the whole schedule is NOT written back: its x and P leave bit for bit as they came (the `_masked` rule). */
+#define RN_DECLARE_BATCH_RUN_PF(name)                                                                            \
+  int RN_FN(name, has_batch_run_pf)(void);                                                                       \
+  int RN_FN(name, batch_run_pf)(double *x, double *P, const double *Q, const int32_t *kinds, const double *dts,   \
+                                int64_t T, double *z, const double *R, int64_t n, int norm_quats, uint8_t *flags, \
+                                double *trace_x, double *trace_P, void *stream);
+
 /* Per-filter timelines, THE LATE OBSERVATION ON THE DEVICE: the rewind of every filter batch_timeline_plan found late, each in its own ring
  * (EKF_sym.rewind and the too-old test in front of it, the reference's ekf_sym.py:418-438, 464-471), and the gather of the
  * overtaken entries, one replay position of all rewound filters at a time, into the buffers batch_predict_update_kinds and

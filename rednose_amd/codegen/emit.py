@@ -46,7 +46,9 @@ SMALL_MAX_E = 7    # lane-per-filter register budget: x, P and the update's temp
 #                      (status ERR_UNSUPPORTED, the step-granular entry points cover such models)
 #   no_kinds           the mixed-kind step kernel (k_kinds: a kind per filter in one launch) touches scratch memory or spills -> library without
 #                      it ({name}_has_step_kinds() == 0, its entry points return ERR_UNSUPPORTED; one `_masked` launch per kind serves such a call)
-FALLBACKS = ("force_wide", "no_model_defaults", "no_rts4", "rts_one_wave", "no_rts", "no_run2", "no_run", "no_run_blk", "no_tri", "no_kinds")
+#   no_run_pf          the fused run with a schedule per filter (k_run_pf / k_run_pf_tr) touches scratch memory or spills -> library without it
+#                      ({name}_has_batch_run_pf() == 0, batch_run_pf returns ERR_UNSUPPORTED; BatchedEKF.run_logs walks such logs step by step)
+FALLBACKS = ("force_wide", "no_model_defaults", "no_rts4", "rts_one_wave", "no_rts", "no_run2", "no_run", "no_run_blk", "no_tri", "no_kinds", "no_run_pf")
 KINDS_MAX = 16      # kinds of a model with a mixed-kind step: the Z table rn::k_timeline_push takes by value
 _active = frozenset()      # fallbacks of the emit() call in progress
 
@@ -67,6 +69,16 @@ def step_kinds(spec, fallbacks=None):
   if "no_kinds" in fb or spec.N > 0 or len(spec.kinds) > KINDS_MAX:
     return False
   return all(k.ea_sym is None and k.He_sym is None and k.zdim < emit_wide2.WIDE_Z_LDS and k.kind > 0 for k in spec.kinds)
+
+
+def run_pf(spec, fallbacks=None):
+  """Does this library get the fused run with a schedule per filter (k_run_pf: emit_small.run_pf_kernel, emit_wide3.run_pf_kernel)?  Models with a
+  fused run whose kinds take no extra arguments, MSCKF models excepted.  (Lane-group models whose batch_run is emit_run2's k_run2 get emit_wide3's
+  single-wavefront kernel, with the functions it needs emitted beside emit_run2's.)"""
+  fb = _active if fallbacks is None else fallbacks
+  if "no_run_pf" in fb or "no_run" in fb or spec.N > 0 or spec.dim_err > 64:
+    return False
+  return all(k.ea_sym is None and k.He_sym is None and k.kind > 0 for k in spec.kinds)
 
 
 def _align2(n):
@@ -154,6 +166,8 @@ GRID_PUSH = "dim3((unsigned)((n + 3) / 4 < 16384 ? (n + 3) / 4 : 16384)), dim3(2
 # parameters of batch_run / batch_run_tri and of batch_rts / batch_rts_tri
 RUN_PARAMS = ("double *x, double *P, const double *Q, const int32_t *kinds, const double *dts, int64_t T, double *z, const double *R, int64_t n, int norm_quats, "
               "uint8_t *flags, double *trace_x, double *trace_P, const double *ea, const int32_t *augment, void *stream")
+RUN_PF_PARAMS = ("double *x, double *P, const double *Q, const int32_t *kinds, const double *dts, int64_t T, double *z, const double *R, int64_t n, int norm_quats, "
+                 "uint8_t *flags, double *trace_x, double *trace_P, void *stream")
 RTS_PARAMS = ("const double *xf, const double *Pf, const double *ts, int64_t T, const double *Q, int64_t n, int norm_quats, double *xs, double *Ps, "
               "const double *x_last, const double *P_last, void *stream")
 
@@ -176,11 +190,11 @@ def _select(spec):
               (use_rts4; emit_rts4: 8 .. 22 error states) or rn::k_rts_group (MSCKF models -- their main block is smoothed, ekf_sym.py:675-686 --,
               larger models, and the fallback of k_rts4)
     use_tri   packed-triangle trace: both structures or neither (batch_run_tri writes what batch_rts_tri reads)
-    has_kinds the mixed-kind step kernel k_kinds"""
+    has_kinds the mixed-kind step kernel k_kinds;  has_run_pf: the fused run with a schedule per filter (k_run_pf)"""
   if spec.dim_err > 64:
     raise NotImplementedError(f"{spec.dim_err} error states: the lane-group kernels hold one row of P per lane of a wavefront (<= 64)")
   tune = tuning.current()
-  s = types.SimpleNamespace(fam=family(spec), has_run="no_run" not in _active, has_kinds=step_kinds(spec))
+  s = types.SimpleNamespace(fam=family(spec), has_run="no_run" not in _active, has_kinds=step_kinds(spec), has_run_pf=run_pf(spec))
   wide = s.fam == "wide"
   s.step = emit_wide2 if wide else emit_small
   s.use_run2 = wide and s.has_run and tune.run2 and "no_run2" not in _active and emit_run2.applicable(spec)
@@ -480,6 +494,12 @@ def _abi_batched(spec, s):
   else:
     launch = emit_small.launch_run(spec) if s.fam == "small" else (emit_run2.launch_run() if s.use_run2 else emit_wide3.launch_run())
   a.fn("int", "batch_run", RUN_PARAMS, _run_body(launch, hip_check=s.has_run))
+  # The fused run with a schedule per filter (k_run_pf): kinds (T, n), dts (T, n), R the per-kind table of batch_predict_update_kinds.  The
+  # symbols exist in every library; without the kernel batch_run_pf returns ERR_UNSUPPORTED.
+  a.fn("int", "has_batch_run_pf", "void", f"return {int(s.has_run_pf)};")
+  a.fn("int", "batch_run_pf", RUN_PF_PARAMS, _run_body(emit_small.launch_run_pf() if s.fam == "small" else emit_wide3.launch_run_pf()) if s.has_run_pf else _unsupported(
+    "batch_run_pf: not generated for this model (MSCKF model, a kind with extra arguments, no fused run, or the kernel "
+    "did not fit the register file)"))
   return a
 
 

@@ -321,23 +321,25 @@ def _flag_acc(D):
 
 def kind_cases(spec, suffix, z, R, R_shared=None, extra="", ea_lane=None, ind=8):
   """The `case {kind}: { .. }` blocks of a switch over the model's kinds.  The observation and its covariance are copied into arrays of the kind's
-  own size -- zk from `z`[i], Rk from the expression `R` in i (R_shared(idx): the expression for `!r_per_filter`, idx the kind's position in the
-  model) --, fl = update_{kind}{suffix}(x, P, zk, Rk ..) runs, the residual goes back to `z`.  `extra`: text behind the call's arguments.  `ea_lane`:
+  own size -- zk from `z`[i], Rk from the expression `R` in i (or R(idx) when callable; R_shared(idx): the expression for `!r_per_filter`, idx the
+  kind's position in the model) --, fl = update_{kind}{suffix}(x, P, zk, Rk ..) runs, the residual goes back to `z`.  `extra`: text behind the call's arguments.  `ea_lane`:
   the lane's filter within the tile in the (T, n, EA) array of per-step extra arguments; a kind that takes them sets flag 8 without the array."""
   pad = " " * ind
   EAM = max(ea_count(k) for k in spec.kinds)
   cases = []
+  R_of = R if callable(R) else (lambda idx: R)      # (k_run_pf: a per-kind table, the expression depends on the kind's position)
   for idx, k in enumerate(spec.kinds):
     Z = k.zdim
+    R_k = R_of(idx)
     ea, guard = "", ""
     if k.ea_sym is not None and ea_lane is not None:
       ea = f", gea + ((int64_t)t * n + base + {ea_lane}) * {EAM}"
       guard = f"{pad}  if (gea == nullptr) {{ fl = 8; break; }}\n"
-    copy_R = f"#pragma unroll\n{pad}  for (int i = 0; i < {Z * Z}; i++) Rk[i] = {R};"
+    copy_R = f"#pragma unroll\n{pad}  for (int i = 0; i < {Z * Z}; i++) Rk[i] = {R_k};"
     if R_shared is not None:
       copy_R = f"""{pad}  if (r_per_filter) {{
 #pragma unroll
-{pad}    for (int i = 0; i < {Z * Z}; i++) Rk[i] = {R};
+{pad}    for (int i = 0; i < {Z * Z}; i++) Rk[i] = {R_k};
 {pad}  }} else {{
 #pragma unroll
 {pad}    for (int i = 0; i < {Z * Z}; i++) Rk[i] = {R_shared(idx)};
@@ -442,6 +444,9 @@ __global__ __launch_bounds__(64) void k_predict(double* __restrict__ gx, double*
     out.append(run_kernel_blk(spec, norm, trace=True))
   else:                            # fallback "no_run_blk" (the blocked kernels spilled): the step-at-a-time k_run serves both
     out.append(run_kernel(spec, norm))
+  if emit.run_pf(spec):            # the fused run with a schedule per filter: k_run_pf (no trace) and k_run_pf_tr (filtered trace)
+    out.append(run_pf_kernel(spec, norm))
+    out.append(run_pf_kernel(spec, norm, trace=True))
   return "\n".join(out)
 
 
@@ -906,6 +911,198 @@ __global__ __launch_bounds__(64) void {kname}(double* __restrict__ gx, double* _
   }}
 }}
 """
+
+
+def run_pf_block(spec):
+  """Steps per block of k_run_pf: run_block's, or run_unroll's where the blocked kernels were dropped (fallback no_run_blk)."""
+  return run_block(spec) or run_unroll(spec)
+
+
+def run_pf_kernel(spec, norm, trace=False):
+  """The fused run with a SCHEDULE PER FILTER (kinds (T, n), dts (T, n)): N independent logs replayed in one launch.  run_kernel_blk's
+  structure -- blocks of K steps in registers, ONE vmcnt(0) per block, y and the flags of block b stored at the start of block b + 1 --
+  with the schedule per lane: the lane of filter i loads its own kinds[t * n + i] and dts[t * n + i] of the next block's K steps with that
+  block's observation rows (coalesced across the lanes; K more int + double registers per buffer), nothing is broadcast, the per-kind
+  table of R sits in LDS beside Q, and the switch over kinds runs per lane as in k_kinds: a wavefront pays for the kinds present among its
+  64 filters.  An idle entry (kind <= 0, flag 16) and an entry whose kind the model does not have (flag 8) skip predict and update: the
+  lane's registers and its z row stay as they are.  A filter without a stepped entry in the whole schedule is not written back: its lane
+  leaves the LDS image as it was loaded (the `_masked` kernels' rule).
+  trace=True: k_run_pf_tr, every step's pair of every filter (stepped or not: the trace is dense) leaves through the LDS image as in
+  k_run_blk_tr; the image of the final write-back is loaded again in front of it, since the trace has overwritten the one that came in."""
+  D, E = spec.dim_x, spec.dim_err
+  EE = E * E
+  zmax = max(k.zdim for k in spec.kinds)
+  ZZ = zmax * zmax
+  NK = len(spec.kinds)
+  K = run_pf_block(spec)
+  cases = kind_cases(spec, "_regs_sym", "cur[u]", lambda idx: f"s_R[{idx * ZZ} + i]", ind=12)
+  known = " ".join(f"case {k.kind}:" for k in spec.kinds)
+  # rows are addressed by pointer increments as in k_run_blk: a row past the end of the schedule re-reads row T - 1
+  issue = f"""{{
+      const int64_t tb0_ = TB_ < T ? TB_ : T - 1;
+      const double* zp_ = zrow + tb0_ * rowstride;
+      const int32_t* kp_ = krow + tb0_ * n;
+      const double* dp_ = drow + tb0_ * n;
+      const int64_t left_ = T - 1 - tb0_;          // rows of the schedule after row tb0_
+#pragma unroll
+      for (int u = 0; u < {K}; u++) {{
+        kn[u] = kp_[0];
+        dtn[u] = dp_[0];
+#pragma unroll
+        for (int i = 0; i < {zmax}; i++) nxt[u][i] = zp_[i];
+        zp_ += (u < left_) ? rowstride : 0;
+        kp_ += (u < left_) ? n : 0;
+        dp_ += (u < left_) ? n : 0;
+      }}
+    }}"""
+  store = f"""#pragma unroll
+          for (int i = 0; i < {zmax}; i++) yp_[i] = cur[u][i];
+          if (flags != nullptr) fp_[0] = (uint8_t)flb[u];
+          yp_ += rowstride;
+          fp_ += n;"""
+  kname = "k_run_pf_tr" if trace else "k_run_pf"
+  title = (f"// ---- fused run, a schedule per filter, with the filtered trace: blocks of {K} steps (see emit_small.run_pf_kernel) ----------------"
+           if trace else
+           f"// ---- fused run, a schedule per filter (kinds (T, n), dts (T, n)): blocks of {K} steps in registers (emit_small.run_pf_kernel) ----")
+  helpers = "" if trace else """
+__device__ __forceinline__ void pin_k(int& v) { asm volatile("" : "+v"(v)); }
+"""
+  targs = ",\n    double* __restrict__ tx, double* __restrict__ tP" if trace else ""
+  tstore = f"""
+          // pair of every filter after step t (an idle filter's is the one it had): through the LDS image, coalesced
+          rn::regs_to_lds<{D}>(s_x, lane, x);
+          rn::regs_to_lds<{EE}>(s_P, lane, P);
+          rn::wave_lds_sync();
+          if (tx != nullptr) rn::tile_l2g<{D}>(tx + (t * n + base) * {D}, cnt, s_x, lane);
+          if (tP != nullptr) rn::tile_l2g<{EE}>(tP + (t * n + base) * {EE}, cnt, s_P, lane);
+          rn::wave_lds_sync();""" if trace else ""
+  reload = f"""
+    // the image the filters came with, again (the trace has overwritten it; x and P in HBM are still untouched)
+    rn::tile_g2l<{D}>(gx + base * {D}, cnt, s_x, lane);
+    rn::tile_g2l<{EE}>(gP + base * {EE}, cnt, s_P, lane);
+    rn::wave_lds_sync();""" if trace else ""
+  return f"""{helpers}
+{title}
+__global__ __launch_bounds__(64) void {kname}(double* __restrict__ gx, double* __restrict__ gP, const double* __restrict__ gQ,
+    const int32_t* __restrict__ kinds, const double* __restrict__ dts, const int64_t T, double* gz,
+    const double* __restrict__ gR, const int64_t n, const int norm_quats, uint8_t* __restrict__ flags{targs}) {{
+{_lds(x=D, P=EE)}
+{_lds(True, Q=EE, R=NK * ZZ)}
+  const int lane = threadIdx.x;
+  for (int i = lane; i < {EE}; i += 64) s_Q[i] = gQ[i];
+  for (int i = lane; i < {NK * ZZ}; i += 64) s_R[i] = gR[i];      // one row per kind, in the order of the model's kinds
+  const int64_t tiles = (n + 63) >> 6;
+  const int64_t rowstride = n * {zmax};               // doubles between the rows of one filter in consecutive steps
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {{
+    const int64_t base = tile << 6;
+    const int cnt = (n - base) < 64 ? (int)(n - base) : 64;
+    rn::tile_g2l<{D}>(gx + base * {D}, cnt, s_x, lane);
+    rn::tile_g2l<{EE}>(gP + base * {EE}, cnt, s_P, lane);
+    rn::wave_lds_sync();
+    double x[{D}], P[{EE}];
+    rn::lds_to_regs<{D}>(s_x, lane, x);
+    rn::lds_to_regs<{EE}>(s_P, lane, P);
+    symmetrize_regs(P);
+    // lanes past the end of a ragged tile follow a copy of the last filter's schedule and rows and store nothing
+    const int lc = lane < cnt ? lane : cnt - 1;
+    const bool live = lane < cnt;
+    double* zrow = gz + (base + lc) * {zmax};
+    const int32_t* krow = kinds + base + lc;
+    const double* drow = dts + base + lc;
+    double cur[{K}][{zmax}], nxt[{K}][{zmax}], dtv[{K}], dtn[{K}];
+    int flb[{K}], kv[{K}], kn[{K}];
+    bool stepped = false;
+    {issue.replace("TB_", "((int64_t)0)")}
+    for (int64_t tb = 0; tb < T; tb += {K}) {{
+      // everything in flight lands: this block's rows and schedule (and the stores issued one block ago)
+#pragma unroll
+      for (int u = 0; u < {K}; u++) {{
+#pragma unroll
+        for (int i = 0; i < {zmax}; i++) rn::pin(nxt[u][i]);
+        rn::pin(dtn[u]);
+        pin_k(kn[u]);
+      }}
+      if (tb > 0 && live) {{
+        double* yp_ = zrow + (tb - {K}) * rowstride;
+        uint8_t* fp_ = flags + (tb - {K}) * n + base + lane;
+#pragma unroll
+        for (int u = 0; u < {K}; u++) {{
+{store}
+        }}
+      }}
+#pragma unroll
+      for (int u = 0; u < {K}; u++) {{
+#pragma unroll
+        for (int i = 0; i < {zmax}; i++) cur[u][i] = nxt[u][i];
+        dtv[u] = dtn[u];
+        kv[u] = kn[u];
+      }}
+      {issue.replace("TB_", f"(tb + {K})")}
+#pragma unroll
+      for (int u = 0; u < {K}; u++) {{
+        const int64_t t = tb + u;
+        flb[u] = 0;
+        if (t < T) {{
+          const int kind = kv[u];
+          int fl = 16;                             // idle entry: no predict, the row passes through
+          if (kind > 0) {{
+            switch (kind) {{
+              {known} {{
+                const double dt = dtv[u];
+                predict_regs_sym(x, P, s_Q, dt);
+                {norm}
+                stepped = true;
+                fl = 0;
+                break;
+              }}
+              default: fl = 8; break;      // not a kind of this model: untouched like an idle entry
+            }}
+          }}
+          if (fl == 0) {{
+            switch (kind) {{
+{cases}
+              default: break;
+            }}
+            {norm}
+          }}
+          flb[u] = fl;{tstore}
+        }}
+      }}
+    }}
+    if (live) {{
+      const int64_t tl = ((T - 1) / {K}) * {K};          // first step of the last block
+      double* yp_ = zrow + tl * rowstride;
+      uint8_t* fp_ = flags + tl * n + base + lane;
+#pragma unroll
+      for (int u = 0; u < {K}; u++) {{
+        if (tl + u < T) {{
+{store}
+        }}
+      }}
+    }}{reload}
+    // a filter that no entry of its schedule stepped keeps the record it came with: its lane does not touch the image
+    if (live && stepped) {{
+      rn::regs_to_lds<{D}>(s_x, lane, x);
+      rn::regs_to_lds<{EE}>(s_P, lane, P);
+    }}
+    rn::wave_lds_sync();
+    rn::tile_l2g<{D}>(gx + base * {D}, cnt, s_x, lane);
+    rn::tile_l2g<{EE}>(gP + base * {EE}, cnt, s_P, lane);
+    rn::wave_lds_sync();
+  }}
+}}
+"""
+
+
+def launch_run_pf():
+  return """  const int64_t tiles = (n + 63) >> 6;
+  if (trace_x == nullptr && trace_P == nullptr) {
+    hipLaunchKernelGGL(k_run_pf, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
+                       x, P, Q, kinds, dts, T, z, R, n, norm_quats, flags);
+  } else {
+    hipLaunchKernelGGL(k_run_pf_tr, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
+                       x, P, Q, kinds, dts, T, z, R, n, norm_quats, flags, trace_x, trace_P);
+  }"""
 
 
 def launch_run(spec=None):

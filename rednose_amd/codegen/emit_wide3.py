@@ -103,7 +103,7 @@ class RunLayout(SlotLayout):
     return self.feature_tail(self.OFF_FL + 1)
 
 
-def predict_fn(spec, qdiag=False):
+def predict_fn(spec, qdiag=False, pf=False):
   """Matrix part of predict on register rows; F's non-trivial entries are broadcast reads of the filter's slot.
 
   P' = F P F^T + dt Q with ONE transposition through LDS: rows of A = P F^T are row-local; under P = P^T the columns of A are the
@@ -115,7 +115,12 @@ def predict_fn(spec, qdiag=False):
   arrive as register operands and no global memory is read.  That matters beyond the 3 R E loads saved: a load's s_waitcnt
   vmcnt also waits for every EARLIER store of the wavefront (the counter retires in order), so with the trace enabled the rows
   of Q fetched here drained the previous step's 32 KB of trace stores on every step -- the only vector load consumed in the
-  middle of a step (profiles/r3a: 11.6 us per step with the trace against 8.7 without)."""
+  middle of a step (profiles/r3a: 11.6 us per step with the trace against 8.7 without).
+
+  pf=True emits `predict_rows_pf` / `predict_rows_qd_pf` for the fused run with a schedule per filter (k_run_pf): the same statements with
+  one more argument, `pd` -- does this lane's GROUP predict at this step? --, and every assignment to a register row selects between
+  the new value and the row as it is.  Every lane walks every statement (and meets every wave_lds_sync); a group that is idle keeps its
+  rows bit for bit.  What such a group writes into its own image of P is scratch (all LDS exchange is group-local)."""
   E = spec.dim_err
   GL, R, _ = layout(spec)
   lay, Fs, _, _ = w2.slot_tables(spec, RunLayout)
@@ -139,7 +144,8 @@ def predict_fn(spec, qdiag=False):
       b += ["#pragma unroll", f"  for (int m = 0; m < {E}; m++) a[m] = sP[m * {E} + rc{s}];      // column of A = row of B"]
       for j in range(E):
         diag = f" + (rc{s} == {j} ? dq{s} : 0.0)" if GL * s <= j < GL * (s + 1) else ""      # the lane's own row index is c + {GL} s
-        b.append(f"  row{s}[{j}] = {sum_terms(term(cf, f'a[{m}]') for m, cf in Fs.row_nz(j))}{diag};")
+        val = f"{sum_terms(term(cf, f'a[{m}]') for m, cf in Fs.row_nz(j))}{diag}"
+        b.append(f"  row{s}[{j}] = pd ? ({val}) : row{s}[{j}];" if pf else f"  row{s}[{j}] = {val};")
       b.append("}")
   else:
     # Q is read from HBM / L2 (no LDS left for it): slot s's row of Q is requested one slot ahead of its use
@@ -154,24 +160,32 @@ def predict_fn(spec, qdiag=False):
       if s + 1 < R:
         b += ["#pragma unroll", f"  for (int j = 0; j < {E}; j++) q{s + 1}[j] = gQ[rc{s + 1} * {E} + j];"]
       for j in range(E):
-        b.append(f"  row{s}[{j}] = {sum_terms(term(cf, f'a[{m}]') for m, cf in Fs.row_nz(j))} + dt*q{s}[{j}];")
+        val = f"{sum_terms(term(cf, f'a[{m}]') for m, cf in Fs.row_nz(j))} + dt*q{s}[{j}]"
+        b.append(f"  row{s}[{j}] = pd ? ({val}) : row{s}[{j}];" if pf else f"  row{s}[{j}] = {val};")
       b.append("}")
   b.append("rn::wave_lds_sync();      // the image is free again")
   b += _tl(9)
   rows = ", ".join(f"double (&row{s})[{E}]" for s in range(R))
   idx = ", ".join(f"const int rr{s}, const int rc{s}, const bool ok{s}" for s in range(R))
+  sfx, pda = ("_pf", ", const bool pd") if pf else ("", "")
   if qdiag:
     qarg = ", ".join(f"const double qd{s}" for s in range(R))
-    head = (f"__device__ __forceinline__ void predict_rows_qd({rows}, double* sP, {qarg}, const double* sl, {idx}{_tl_arg()}) {{")
+    head = (f"__device__ __forceinline__ void predict_rows_qd{sfx}({rows}, double* sP, {qarg}, const double* sl, {idx}{pda}{_tl_arg()}) {{")
   else:
-    head = (f"__device__ __forceinline__ void predict_rows({rows}, double* sP, const double* __restrict__ gQ, const double* sl, {idx}{_tl_arg()}) {{")
+    head = (f"__device__ __forceinline__ void predict_rows{sfx}({rows}, double* sP, const double* __restrict__ gQ, const double* sl, {idx}{pda}{_tl_arg()}) {{")
   return "\n".join([head] + ind(b) + ["}"])
 
 
-def update_fn(spec, k):
+def update_fn(spec, k, pf=False):
   """Matrix part of the update of kind k on register rows.  y, the non-trivial entries of He = H H_mod and, for feature-track
   kinds, the Householder reflectors and the projected noise are read from the filter's slot (phase 1 put them there); dx and
-  the gate / rank flags go back to it."""
+  the gate / rank flags go back to it.
+
+  pf=True emits `update_{kind}_rows_pf` for k_run_pf, with one more argument: `mine` -- does this lane's GROUP carry this kind at this step?
+  Every lane walks every statement; a group that is idle, flagged 8 or of another kind puts zeros where G and K^T go in its own buffer and
+  takes zero coefficients into both rank-Z passes (row -+= 0 * 0: the rows come out unchanged, whatever stale numbers its slot holds), and
+  writes nothing into its slot."""
+  assert not (pf and k.He_sym is not None)
   E, Zf = spec.dim_err, k.zdim
   _, R, _ = layout(spec)
   lay, _, Hss, _ = w2.slot_tables(spec, RunLayout)
@@ -195,6 +209,8 @@ def update_fn(spec, k):
       b.append(f"double kk{s}[{Z}] = {{{', '.join(f't0_{s}[{EADIM + zi}]' for zi in range(Z))}}};")
     else:
       b.append(f"double kk{s}[{Z}] = {{" + ", ".join(sum_terms(term(cf, f'row{s}[{kk}]') for kk, cf in Hs.row_nz(zi)) for zi in range(Z)) + "};")
+    if pf:
+      b += [f"if (!mine) {{", "#pragma unroll", f"  for (int i = 0; i < {Z}; i++) kk{s}[i] = 0.0;", "}"]
     b.append(f"if (ok{s}) {{ " + " ".join(f"sG[{zi} * {E} + rr{s}] = kk{s}[{zi}];" for zi in range(Z)) + " }")
   b.append("rn::wave_lds_sync();")
   b += _tl(10)
@@ -221,6 +237,8 @@ def update_fn(spec, k):
     b.append(f"rn::spd_solve<{Z}>(L, iL, kk{s});                       // K[row][:]")
     if feat:     # the reference's numpy path ignores a measurement whose null-space projection failed (ekf_sym.py:589-591)
       b += ["if (rank_deficient != 0.0) {", "#pragma unroll", f"  for (int i = 0; i < {Z}; i++) kk{s}[i] = 0.0;", "}"]
+    if pf:      # (S = R for such a group: the solve above ran on zeros)
+      b += [f"if (!mine) {{", "#pragma unroll", f"  for (int i = 0; i < {Z}; i++) kk{s}[i] = 0.0;", "}"]
     b.append(f"const double dx{s} = " + " + ".join(f"kk{s}[{zi}]*sl[{(lay.OFF_YP if feat else lay.OFF_Y) + zi}]" for zi in range(Z)) + ";")
   # B = P - K G: every broadcast row of G feeds all R row slots
   b += _tl(12)
@@ -234,12 +252,14 @@ def update_fn(spec, k):
     for zi in range(Z):
       c = f"Cf{s}[{EADIM + zi}]" if feat else sum_terms(term(cf, f"row{s}[{j}]") for j, cf in Hs.row_nz(zi))
       kr = " + ".join(f"kk{s}[{w}]*Rl[{w * Z + zi}]" for w in range(Z))
-      b.append(f"Dm{s}[{zi}] = " + ("rank_deficient != 0.0 ? 0.0 : " if feat else "") + f"({kr}) - ({c});")
+      b.append(f"Dm{s}[{zi}] = " + ("rank_deficient != 0.0 ? 0.0 : " if feat else "") + ("!mine ? 0.0 : " if pf else "") + f"({kr}) - ({c});")
   b.append("rn::wave_lds_sync();      // every lane has taken G (and y): the buffer takes K^T, the slot takes dx and the flags")
   fl = "(double)gated + rank_deficient" if feat else "(double)gated"
   for s in range(R):
-    b.append(f"if (ok{s}) {{ " + " ".join(f"sG[{zi} * {E} + rr{s}] = kk{s}[{zi}];" for zi in range(Z)) + f" sw[{lay.OFF_DX} + rr{s}] = dx{s};" +
-             (f" if (rr{s} == 0) sw[{lay.OFF_FL}] = {fl};" if s == 0 else "") + " }")
+    slot = f" sw[{lay.OFF_DX} + rr{s}] = dx{s};" + (f" if (rr{s} == 0) sw[{lay.OFF_FL}] = {fl};" if s == 0 else "")
+    if pf:
+      slot = f" if (mine) {{{slot} }}"
+    b.append(f"if (ok{s}) {{ " + " ".join(f"sG[{zi} * {E} + rr{s}] = kk{s}[{zi}];" for zi in range(Z)) + slot + " }")
   b.append("rn::wave_lds_sync();")
   b += _tl(14)
   b += rank_pass(E, Z, R, "sG", "+=", "Dm")
@@ -247,8 +267,8 @@ def update_fn(spec, k):
   b.append("rn::wave_lds_sync();      // the broadcast buffer is free again")
   rows = ", ".join(f"double (&row{s})[{E}]" for s in range(R))
   idx = ", ".join(f"const int rr{s}, const int rc{s}, const bool ok{s}" for s in range(R))
-  head = (f"__device__ __forceinline__ void update_{k.kind}_rows({rows}, const double* __restrict__ gR, double* sP, "
-          f"double* sG, const double* sl, double* sw, {idx}{_tl_arg()}) {{")
+  head = (f"__device__ __forceinline__ void update_{k.kind}_rows{'_pf' if pf else ''}({rows}, const double* __restrict__ gR, double* sP, "
+          f"double* sG, const double* sl, double* sw, {idx}{', const bool mine' if pf else ''}{_tl_arg()}) {{")
   return "\n".join([head] + ind(b) + ["}"])
 
 
@@ -260,14 +280,22 @@ def kernels(spec, with_run=True):
   GL, R, FPW = layout(spec)
   scal_text, lay = w2.device_functions(spec, lay_cls=RunLayout, sfx="_r")
   if not with_run:
+    from rednose_amd.codegen import emit      # (emit imports this module)
+    # the model's batch_run is emit_run2's k_run2; the fused run with a schedule per filter is this module's single-wavefront structure:
+    # the scalar phases against RunLayout, the predicated matrix phases and k_run_pf follow the constants
+    pf = ["", scal_text, "", predict_fn(spec, pf=True), predict_fn(spec, qdiag=True, pf=True)] + [update_fn(spec, k, pf=True) for k in spec.kinds] + \
+         [run_pf_kernel(spec)] if emit.run_pf(spec) else []
     return "\n".join([f"constexpr int GLR = {GL};    // fused run: lanes per filter", f"constexpr int RPL = {R};    // rows of P per lane",
-                      f"constexpr int FPWR = {FPW};   // filters per wavefront", f"constexpr int SLOT_R = {lay.SLOT};   // doubles per scalar slot of the single-wavefront layout", ""])
+                      f"constexpr int FPWR = {FPW};   // filters per wavefront", f"constexpr int SLOT_R = {lay.SLOT};   // doubles per scalar slot of the single-wavefront layout", ""] + pf)
   out = [f"constexpr int GLR = {GL};    // fused run: lanes per filter", f"constexpr int RPL = {R};    // rows of P per lane",
          f"constexpr int FPWR = {FPW};   // filters per wavefront", f"constexpr int SLOT_R = {lay.SLOT};   // fused run: doubles per scalar slot",
          "", scal_text, "", predict_fn(spec), predict_fn(spec, qdiag=True)]
   for k in spec.kinds:
     out.append(update_fn(spec, k))
   out.append(run_kernel(spec))
+  from rednose_amd.codegen import emit      # (emit imports this module)
+  if emit.run_pf(spec):            # the fused run with a schedule per filter: predicated matrix phases + k_run_pf
+    out += [predict_fn(spec, pf=True), predict_fn(spec, qdiag=True, pf=True)] + [update_fn(spec, k, pf=True) for k in spec.kinds] + [run_pf_kernel(spec)]
   return "\n".join(out)
 
 
@@ -492,6 +520,169 @@ __global__ __launch_bounds__(64) void k_run(double* __restrict__ gx, double* __r
   }}
 }}
 """
+
+
+def run_pf_kernel(spec):
+  """k_run_pf of the lane-group family: k_run's structure (GL lanes per filter, rows of P in registers, FPW filters per wavefront) with a
+  SCHEDULE PER FILTER, kinds (T, n) and dts (T, n).  Every lane of a group fetches its filter's kind and dt (one address per group), a step
+  ahead like the observations.  The scalar phases run on lane c == 0 of the groups that step, each on its own kind and dt.  The matrix phases
+  are the predicated functions (predict_fn / update_fn with pf=True): predict runs when any group of the wavefront predicts, and for every
+  kind present among the wavefront's filters (a wave-uniform test) that kind's rows update runs on all lanes, changing the rows of the
+  groups that carry it.  An idle group (kind <= 0, flag 16) and a group whose kind the model does not have (flag 8) keep slot and rows.
+  A filter that no entry stepped is not written back: the image of the final store is the one that came in, loaded again, and only the
+  groups that stepped put their rows into it.  Above 32 error states a filter owns the wavefront and the tests are uniform anyway."""
+  D, E = spec.dim_x, spec.dim_err
+  EE = E * E
+  GL, R, FPW = layout(spec)
+  lay = w2.slot_tables(spec, RunLayout)[0]
+  zmax = max(k.zdim for k in spec.kinds)
+  ZZ = zmax * zmax
+  NZ = -(-(FPW * zmax) // 64)
+  q_ = range(NZ)
+  z_decl = " ".join(f"const int zf{q} = (lane + {64 * q}) / {zmax}, zc{q} = (lane + {64 * q}) % {zmax};" for q in q_)
+  z_tile_a = "".join(f"    const bool zlive{q} = zf{q} < cnt;\n" for q in q_)
+  z_tile_b = "".join(f"    double* slz{q} = s_sl + (zlive{q} ? zf{q} : 0) * SLOT_R + {lay.OFF_Y} + zc{q};\n" for q in q_)
+  z_first = "\n".join(f"    if (zlive{q}) *slz{q} = gz[base * {zmax} + lane + {64 * q}];" for q in q_)
+  z_next = "\n".join([f"      double zn[{NZ}] = {{{', '.join('0.0' for _ in q_)}}};                 // next step's observations, in flight during this step"] +
+                     [f"      if (t + 1 < T && zlive{q}) zn[{q}] = gz[((t + 1) * n + base) * {zmax} + lane + {64 * q}];" for q in q_])
+  z_out = "\n".join(f"      if (zlive{q}) gz[(t * n + base) * {zmax} + lane + {64 * q}] = *slz{q};" for q in q_)
+  z_commit = "\n".join(f"      if (zlive{q}) *slz{q} = zn[{q}];" for q in q_)
+  rows = ", ".join(f"row{s}" for s in range(R))
+  idx = ", ".join(f"rr{s}, rc{s}, ok{s}" for s in range(R))
+  nlc = chr(10)
+  known = " ".join(f"case {k.kind}:" for k in spec.kinds)
+  scal_cases = nlc.join(f"          case {k.kind}: scal_obs_{k.kind}_r(sl, sl + {lay.OFF_Y}); break;" for k in spec.kinds)
+  mat = nlc.join(f"""      {{
+        const bool mine = step && kind == {k.kind};
+        if (__any(mine)) update_{k.kind}_rows_pf({rows}, gR + {i * ZZ}, sP, s_G + gg * {zmax * E}, sl, sl, {idx}, mine{_tl_arg(True)});
+      }}""" for i, k in enumerate(spec.kinds))
+
+  def img(cond):
+    return "\n".join(f"        if (ok{s}{cond}) {{\n#pragma unroll\n          for (int j = 0; j < {E}; j++) sP[rr{s} * {E} + j] = row{s}[j];\n        }}" for s in range(R))
+  id0_guard = "true" if not spec.identity_at_dt0() else "dt != 0.0"
+  nt_trace = "true" if tuning.current().nt_trace else "false"
+  qd_decl = "\n".join(f"  const double qd{s} = gQ[((c + {GL * s}) < {E} ? (c + {GL * s}) : 0) * {E + 1}];" for s in range(R))
+  qd_args = ", ".join(f"qd{s}" for s in range(R))
+  decl_rows = "\n".join(f"    double row{s}[{E}];" for s in range(R))
+  decl_idx = "\n".join(f"    const int rr{s} = c + {GL * s}; const bool ok{s} = live && rr{s} < {E}; const int rc{s} = rr{s} < {E} ? rr{s} : 0;" for s in range(R))
+  load_rows = "\n".join(f"#pragma unroll\n    for (int j = 0; j < {E}; j++) row{s}[j] = 0.5 * (sP[rc{s} * {E} + j] + sP[j * {E} + rc{s}]);" for s in range(R))
+  return f"""
+// ---- fused multi-step run, a schedule per filter: kinds (T, n), dts (T, n); z is (T, n, {zmax}) in: z, out: y; gR one row per kind -----------
+// k_run's phases per step; a group takes part in those its own entry asks for (see emit_wide3.run_pf_kernel).
+__global__ __launch_bounds__(64) void k_run_pf(double* __restrict__ gx, double* __restrict__ gP, const double* __restrict__ gQ,
+    const int32_t* __restrict__ kinds, const double* __restrict__ dts, const int64_t T, double* __restrict__ gz,
+    const double* __restrict__ gR, const int64_t n, const int norm_quats, uint8_t* __restrict__ flags,
+    double* __restrict__ tx, double* __restrict__ tP) {{
+  __shared__ __attribute__((aligned(16))) double s_P[FPWR * {EE} + 2];      // one image of P per filter
+  __shared__ __attribute__((aligned(16))) double s_G[FPWR * {zmax * E}];     // G, then K^T
+  __shared__ __attribute__((aligned(16))) double s_sl[FPWR * SLOT_R];
+  const int lane = threadIdx.x;
+  const int g = lane / GLR;
+  const int c = lane % GLR;
+  {z_decl}
+  int qoff = 0;
+  for (int i = lane; i < {EE}; i += 64) qoff |= (i / {E} != i % {E}) && (gQ[i] != 0.0);
+  const bool qdiag = !__any(qoff);
+{qd_decl}
+  const int64_t tiles = (n + FPWR - 1) / FPWR;
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {{
+    const int64_t base = tile * FPWR;
+    const int cnt = (n - base) < FPWR ? (int)(n - base) : FPWR;
+    const int gg = g < cnt ? g : 0;
+    const bool live = g < cnt;
+{z_tile_a}    double* sP = s_P + gg * {EE};
+    double* sl = s_sl + gg * SLOT_R;
+{z_tile_b}{decl_idx}
+    int lb = lane;
+    asm volatile("" : "+v"(lb));
+    rn::copy_g2l<FPWR * {EE}>(gP + base * {EE}, cnt * {EE}, s_P, lb);
+    for (int i = lane; i < cnt * {D}; i += 64) s_sl[(i / {D}) * SLOT_R + {lay.OFF_X} + i % {D}] = gx[base * {D} + i];
+{z_first}
+    rn::wave_lds_sync();
+{decl_rows}
+{load_rows}
+    bool stepped = false;
+    // the group's own schedule entry, a step ahead (every lane of a group reads its filter's: one address per group)
+    int kind_n = kinds[base + gg];
+    double dt_n = dts[base + gg];
+    for (int64_t t = 0; t < T; t++) {{
+{z_next}
+      const int kind = live ? kind_n : 0;
+      const double dt = dt_n;
+      {{
+        const int64_t tn = t + 1 < T ? t + 1 : t;
+        kind_n = kinds[tn * n + base + gg];
+        dt_n = dts[tn * n + base + gg];
+      }}
+      bool step = false;
+      switch (kind) {{ {known} step = true; break; default: break; }}
+      const bool pd = step && ({id0_guard});
+      stepped = stepped || step;
+      // ---- phase 1a / 2a: predict, per group on its own dt ----
+      if (c == 0 && step) {{
+        if (pd) scal_predict_r(sl + {lay.OFF_X}, dt, sl, norm_quats);
+        else scal_keep_r(sl + {lay.OFF_X}, sl, norm_quats);                 // predict(dt = 0) still renormalises
+      }}
+      rn::wave_lds_sync();
+      if (__any(pd)) {{
+        if (qdiag) {{
+          predict_rows_qd_pf({rows}, sP, {qd_args}, sl, {idx}, pd{_tl_arg(True)});
+        }} else {{
+          int qz = 0;
+          asm volatile("" : "+v"(qz));
+          predict_rows_pf({rows}, sP, gQ + qz, sl, {idx}, pd{_tl_arg(True)});
+        }}
+      }}
+      // ---- phase 1b / 2b: update, every kind present among the wavefront's filters ----
+      if (c == 0 && step) {{
+        switch (kind) {{
+{scal_cases}
+          default: break;
+        }}
+      }}
+      rn::wave_lds_sync();
+{mat}
+      // ---- phase 3: lane 0 of each group injects the error state ----
+      if (c == 0 && live) {{
+        int fl = kind <= 0 ? 16 : 8;          // idle entry; a kind the model does not have: untouched either way
+        if (step) fl = scal_inject_r(sl, sl + {lay.OFF_X}, norm_quats) | (int)sl[{lay.OFF_FL}];
+        if (flags != nullptr) flags[t * n + base + g] = (uint8_t)fl;
+      }}
+      rn::wave_lds_sync();
+{z_out}
+      int lz = lane;
+      asm volatile("" : "+v"(lz));
+      if (tx != nullptr) {{
+        for (int i = lz; i < cnt * {D}; i += 64) tx[(t * n + base) * {D} + i] = s_sl[(i / {D}) * SLOT_R + {lay.OFF_X} + i % {D}];
+      }}
+      if (tP != nullptr) {{
+{img("")}
+        rn::wave_lds_sync();
+        rn::copy_l2g<FPWR * {EE}, {nt_trace}>(tP + (t * n + base) * {EE}, cnt * {EE}, s_P, lz);
+      }}
+      rn::wave_lds_sync();
+{z_commit}
+      rn::wave_lds_sync();
+    }}
+    // the image the filters came with, again: a filter that no entry stepped leaves as it came (x: its slot was never written)
+    int le = lane;
+    asm volatile("" : "+v"(le));
+    rn::copy_g2l<FPWR * {EE}>(gP + base * {EE}, cnt * {EE}, s_P, le);
+    rn::wave_lds_sync();
+{img(" && stepped")}
+    rn::wave_lds_sync();
+    rn::copy_l2g<FPWR * {EE}>(gP + base * {EE}, cnt * {EE}, s_P, le);
+    for (int i = le; i < cnt * {D}; i += 64) gx[base * {D} + i] = s_sl[(i / {D}) * SLOT_R + {lay.OFF_X} + i % {D}];
+    rn::wave_lds_sync();
+  }}
+}}
+"""
+
+
+def launch_run_pf():
+  return """  const int64_t tiles = (n + FPWR - 1) / FPWR;
+  hipLaunchKernelGGL(k_run_pf, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
+                     x, P, Q, kinds, dts, T, z, R, n, norm_quats, flags, trace_x, trace_P);"""
 
 
 def launch_run():

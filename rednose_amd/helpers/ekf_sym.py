@@ -71,8 +71,15 @@ def gen_code(folder, name, f_sym, dt_sym, x_sym, obs_eqs, dim_x, dim_err, eskf_p
 
     usage, bad = build()
     if not os.environ.get("RN_ALLOW_SPILLS"):
+      def drop_run_pf():
+        # this kernel alone is dropped, every other structure of the model stays as it is ({name}_has_batch_run_pf() == 0): checked on the first
+        # build and again behind no_run_blk, which re-emits k_run_pf with another block size -- never left to force_wide or no_run below
+        pf_bad = [k for k in bad if k.startswith("k_run_pf")]
+        return fall_back("no_run_pf", f"the fused run with a schedule per filter {pf_bad} does not fit the register file: library without it") if pf_bad else (usage, bad)
+      usage, bad = drop_run_pf()
       if "k_run_blk" in bad or "k_run_blk_tr" in bad:
         usage, bad = fall_back("no_run_blk", "a blocked fused run spills registers: the step-at-a-time k_run serves fused runs instead")
+        usage, bad = drop_run_pf()
       if bad and rn_emit.family(spec, ()) == "small":
         usage, bad = fall_back("force_wide", f"lane-per-filter kernels {bad} spill registers: regenerating in the lane-group family")
       if "k_rts4" in bad:
@@ -1660,6 +1667,138 @@ class BatchedEKF:
       if augment is not None and augment[t]:
         self._call("batch_augment", self._p(xv), self._p(Pv), nb, self._stream())
       self._keepalive_step = (zt, Rt, eat)
+
+  # -- N independent logs in one launch ---------------------------------------------------------------
+  def _has_batch_run_pf(self):
+    fn = getattr(self._lib, f"{self.name}_has_batch_run_pf", None)
+    return fn is not None and int(fn()) == 1
+
+  def run_logs(self, ts, kinds, zs, Rs, trace=False, flags=False, out=None, exact=False):
+    """Replay N recorded logs, one per filter, in ONE launch ({name}_batch_run_pf: the fused run with a schedule per filter; objects built
+    with per_filter=True).  ts (T, N): the time of entry t of filter i's log, NaN where the filter has none; kinds (T, N) ints, <= 0 = no
+    entry (idle); zs (T, N, zmax): the first Z of a row are the observation, consumed -- overwritten by the residual, the rest of the row and
+    the rows of idle entries pass through --; Rs {kind: (Z, Z)} shared by the entries of a kind.  trace / flags / out as run(): the trace is
+    dense (an idle entry's row is the pair its filter had).  Returns (ys, trace_x, trace_P, flags); flags (T, N): 16 at idle entries.
+
+    Every filter predicts from its own time (filter_times(); a filter that has not started takes dt = 0 on its first entry, the rule of
+    batch_timeline_plan) over its own previous entry.  A log must be in time order and must not start before its filter's time: a fused run
+    does not rewind -- sort the log first (stable, by time).  A kind no filter of the model has raises KeyError, as in run().  Afterwards
+    filter_times()[i] is the time of filter i's last entry, unchanged for a filter without one, and such a filter's x and P are untouched.
+    With rewind_to_keep > 0 the rings are emptied as by reset_rewind(): their checkpoints are no longer the filters' past, so a later
+    observation older than the run is "too old" by the usual rule.  pf_stats and rewind_stats do not count this call.
+    The covariance is read as (P + P^T) / 2, the fused runs' contract.  exact=True, or a library without the kernel
+    ({name}_has_batch_run_pf() == 0: MSCKF models, kinds with extra arguments, models without a fused run), walks the same schedule with the step-granular entry points, one
+    batch_predict_update_kinds launch per step where the library has it, else one `_masked` launch per kind present in the step; exact=True
+    leaves an asymmetric P as it is, like run(exact=True).  Kinds that take extra arguments are not served."""
+    torch = self._torch
+    if not self.per_filter:
+      raise KalmanError("run_logs replays per-filter timelines: construct the orchestrator with per_filter=True")
+    N, zmax = self.batch, max(self.zdims.values())
+    tt = self._dev(ts)
+    if tt.ndim != 2 or tt.shape[1] != N:
+      raise KalmanError(f"run_logs: ts must be (T, N) = (T, {N}), got {tuple(tt.shape)}")
+    T = int(tt.shape[0])
+    if isinstance(kinds, torch.Tensor):
+      kd = kinds.to(device=self.device, dtype=torch.int32)
+      present = [int(k) for k in torch.unique(kd).tolist() if int(k) > 0]
+    else:
+      kh = np.array(kinds, dtype=np.int32)      # (a writable copy: torch does not take read-only arrays)
+      present = [int(k) for k in np.unique(kh) if int(k) > 0]
+      kd = torch.as_tensor(kh).to(self.device)
+    if tuple(kd.shape) != (T, N):
+      raise KalmanError(f"run_logs: kinds must be (T, N) = ({T}, {N}), got {tuple(kd.shape)}")
+    kd = kd.contiguous()
+    if T == 0:
+      return self._dev(zs, (0, N, zmax)), None, None, None
+    for k in present:
+      if k not in self.zdims or k not in Rs:
+        raise KeyError(k)
+      if self.eadims.get(k, 0):
+        raise KalmanError(f"run_logs: kind {k} takes extra arguments, which a per-filter schedule does not carry")
+    tab = np.zeros((len(self.kinds), zmax * zmax))
+    for i, k in enumerate(self.kinds):
+      if k in Rs:
+        Z = self.zdims[k]
+        tab[i, :Z * Z] = np.asarray(Rs[k], dtype=np.float64).reshape(Z * Z)
+    Rd = self._dev(tab)
+    # every entry's dt from its filter's previous entry (or the filter's time in front of the first one): a forward fill along T
+    has = kd > 0
+    ft0 = self.filter_times()
+    idx = torch.where(has, torch.arange(T, device=self.device)[:, None], torch.full((1, 1), -1, dtype=torch.int64, device=self.device))
+    last = torch.cummax(idx, dim=0).values                                         # (T, N): the latest entry of filter i up to step t, -1: none yet
+    prev = torch.cat([torch.full((1, N), -1, dtype=torch.int64, device=self.device), last[:-1]], 0)
+    t_prev = torch.where(prev >= 0, tt.gather(0, prev.clamp(min=0)), ft0[None, :])
+    dts = torch.where(has, torch.nan_to_num(tt - t_prev, nan=0.0), torch.zeros_like(tt)).contiguous()
+    bad = has & (torch.isnan(tt) | (tt < t_prev))
+    if bool(bad.any()):
+      t_, i_ = (int(v) for v in bad.nonzero()[0])
+      if bool(torch.isnan(tt[t_, i_])):
+        raise KalmanError(f"run_logs: filter {i_}, step {t_}: kind {int(kd[t_, i_])} without a time (ts is NaN there; NaN marks idle entries, whose kind is <= 0)")
+      raise KalmanError(f"run_logs: filter {i_}, step {t_}: time {float(tt[t_, i_])} lies before the filter's previous time {float(t_prev[t_, i_])} "
+                        "-- sort the log: a fused run does not rewind")
+    ft_new = torch.where(last[-1] >= 0, tt.gather(0, last[-1:].clamp(min=0))[0], ft0).contiguous()
+    zs = self._dev(zs, (T, N, zmax))
+    if out is not None:
+      tx, tP = out
+      for t_, shp in ((tx, (T, N, self.dim_x)), (tP, (T, N, self.dim_err, self.dim_err))):
+        assert t_.is_contiguous() and t_.dtype == torch.float64 and tuple(t_.shape) == shp and t_.device == self.device, "out: wrong trace buffer"
+    else:
+      tx = torch.empty((T, N, self.dim_x), dtype=torch.float64, device=self.device) if trace else None
+      tP = torch.empty((T, N, self.dim_err, self.dim_err), dtype=torch.float64, device=self.device) if trace else None
+    fl = torch.zeros((T, N), dtype=torch.uint8, device=self.device) if flags else None
+    if self._has_batch_run_pf() and not exact:
+      self._call("batch_run_pf", self._p(self.x), self._p(self.P), self._p(self.Q), self._p(kd), self._p(dts), T, self._p(zs), self._p(Rd), N,
+                 self.norm_quats, self._p(fl), self._p(tx), self._p(tP), self._stream())
+    else:
+      self._run_logs_stepwise(kd, dts, zs, Rd, fl, tx, tP, symmetrise=not exact)
+    self.filter_time = ft_new
+    self._ft_dev = None
+    if self.rewind_to_keep > 0:
+      self.reset_rewind()
+    self._keepalive = (kd, dts, Rd)
+    return zs, tx, tP, fl
+
+  def _run_logs_stepwise(self, kd, dts, zs, Rd, fl, tx, tP, symmetrise=True):
+    """run_logs() for a library without the fused kernel, and run_logs(exact=True): the same per-filter schedule, step by step."""
+    torch = self._torch
+    T, N = kd.shape
+    mixed = self._has_step_kinds()
+    if symmetrise:      # the fused kernel's contract: (P + P^T) / 2 for every filter that steps, a filter without an entry leaves as it came
+      stepped = (kd > 0).any(dim=0)
+      self.P.copy_(torch.where(stepped[:, None, None], 0.5 * (self.P + self.P.transpose(1, 2)), self.P))
+    kh = None if mixed else kd.cpu().numpy()
+    flt = torch.zeros(N, dtype=torch.uint8, device=self.device)
+    keep = []
+    for t in range(T):
+      a8 = (kd[t] > 0).to(torch.uint8)
+      dt = dts[t].clone()
+      zt = zs[t].clone()                   # own allocation: the C ABI wants 16-byte aligned observations
+      if mixed:
+        kt = kd[t].clone()
+        self._call("batch_predict_update_kinds", self._p(self.x), self._p(self.P), self._p(self.Q), self._p(dt), 0.0, self._p(kt), self._p(zt), self._p(Rd), 0,
+                   N, self.norm_quats, self._p(flt), self._p(a8), self._stream())
+        keep = [(kt, a8, dt, zt)]      # (the stream orders the launches: the previous step's buffers may go)
+      else:
+        flt.fill_(16)
+        for k in (int(k_) for k_ in np.unique(kh[t]) if int(k_) > 0):
+          Z = self.zdims[k]
+          m8 = (kd[t] == k).to(torch.uint8)
+          zk = zt[:, :Z].contiguous()
+          Rk = Rd[self.kinds.index(k), :Z * Z].clone()
+          fk = torch.zeros(N, dtype=torch.uint8, device=self.device)
+          self._call(f"batch_predict_update_{k}_masked", self._p(self.x), self._p(self.P), self._p(self.Q), self._p(dt), 0.0, self._p(zk), self._p(Rk), 0,
+                     None, N, self.norm_quats, self._p(fk), self._p(m8), self._stream())
+          zt[:, :Z] = torch.where(m8[:, None] != 0, zk, zt[:, :Z])
+          flt.copy_(torch.where(m8 != 0, fk, flt))
+          keep = keep[-len(self.kinds):] + [(m8, zk, Rk, fk, dt)]
+      zs[t].copy_(zt)
+      if fl is not None:
+        fl[t].copy_(flt)
+      if tx is not None:
+        tx[t].copy_(self.x)
+      if tP is not None:
+        tP[t].copy_(self.P)
+    self._keepalive_step = keep
 
   # -- offline smoothing ----------------------------------------------------------------------------
   def smooth(self, ts, kinds, zs, Rs, passes=1, chunk=None, norm_quats=None, on_chunk=None, flags=False, extra_args=None, augment=None, packed=False):
