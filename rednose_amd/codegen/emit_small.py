@@ -744,6 +744,129 @@ __global__ __launch_bounds__(64) void k_run(double* __restrict__ gx, double* __r
 """
 
 
+def _blocked_run(spec, norm, trace, K, *, kname, title, ragged_note, step, trace_note, helpers="", args="", unused="", lds=None, fill="",
+                 sched_ptrs="", decl_d="", decl_i="", decl_more="", issue_sched="", issue_ptrs="", issue_row="", issue_step="",
+                 pin_row="", pin_block="", rot_row="", rot_block="", reload_note="", wb_guard=""):
+  """The text of a blocked fused run, once: kernel head, LDS, tile prologue, the block loop (everything in flight lands, the previous block's y
+  and flags leave, the registers rotate, the next block is requested, K steps run), the last block's tail and the write-back.  The keyword
+  arguments are the fragments in which the kernels of a shared schedule (run_kernel_blk) and of a schedule per filter (run_pf_kernel) differ:
+  names, arguments and LDS tables, the schedule's registers with their part of `issue`, of the pins and of the rotation (`_row`: per step
+  of the block, `_block`: once per block), the body of a step, and the reload and guard of the write-back."""
+  D, E = spec.dim_x, spec.dim_err
+  EE = E * E
+  zmax = max(k.zdim for k in spec.kinds)
+  load_img = f"""    rn::tile_g2l<{D}>(gx + base * {D}, cnt, s_x, lane);
+    rn::tile_g2l<{EE}>(gP + base * {EE}, cnt, s_P, lane);
+    rn::wave_lds_sync();"""
+
+  def to_lds(pad):
+    return f"{pad}rn::regs_to_lds<{D}>(s_x, lane, x);\n{pad}rn::regs_to_lds<{EE}>(s_P, lane, P);"
+  # rows are addressed by pointer increments (one 64-bit multiply per block, none per row): a row past the end of the schedule
+  # re-reads row T - 1 (the increment is zero there), so the loads stay unconditional
+  issue = f"""{{
+      const int64_t tb0_ = TB_ < T ? TB_ : T - 1;{issue_sched}
+      const double* zp_ = zrow + tb0_ * rowstride;{issue_ptrs}
+      const int64_t left_ = T - 1 - tb0_;          // rows of the schedule after row tb0_
+#pragma unroll
+      for (int u = 0; u < {K}; u++) {{{issue_row}
+#pragma unroll
+        for (int i = 0; i < {zmax}; i++) nxt[u][i] = zp_[i];
+        zp_ += (u < left_) ? rowstride : 0;{issue_step}
+      }}
+    }}"""
+  store = f"""#pragma unroll
+          for (int i = 0; i < {zmax}; i++) yp_[i] = cur[u][i];
+          if (flags != nullptr) fp_[0] = (uint8_t)flb[u];
+          yp_ += rowstride;
+          fp_ += n;"""
+  targs = ",\n    double* __restrict__ tx, double* __restrict__ tP" if trace else ""
+  tstore = f"""
+          {trace_note}
+{to_lds(" " * 10)}
+          rn::wave_lds_sync();
+          if (tx != nullptr) rn::tile_l2g<{D}>(tx + (t * n + base) * {D}, cnt, s_x, lane);
+          if (tP != nullptr) rn::tile_l2g<{EE}>(tP + (t * n + base) * {EE}, cnt, s_P, lane);
+          rn::wave_lds_sync();""" if trace else ""
+  reload = f"\n    {reload_note}\n{load_img}" if trace and reload_note else ""
+  write_back = f"{wb_guard} {{\n{to_lds(' ' * 6)}\n    }}" if wb_guard else to_lds(" " * 4)
+  return f"""{helpers}
+{title}
+__global__ __launch_bounds__(64) void {kname}(double* __restrict__ gx, double* __restrict__ gP, const double* __restrict__ gQ,
+    const int32_t* __restrict__ kinds, const double* __restrict__ dts, const int64_t T, double* gz,
+    const double* __restrict__ gR, const int64_t n, const int norm_quats, uint8_t* __restrict__ flags{args}{targs}) {{{unused}
+{_lds(x=D, P=EE)}
+{_lds(True, Q=EE, **(lds or {}))}
+  const int lane = threadIdx.x;
+  for (int i = lane; i < {EE}; i += 64) s_Q[i] = gQ[i];{fill}
+  const int64_t tiles = (n + 63) >> 6;
+  const int64_t rowstride = n * {zmax};               // doubles between the rows of one filter in consecutive steps
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {{
+    const int64_t base = tile << 6;
+    const int cnt = (n - base) < 64 ? (int)(n - base) : 64;
+{load_img}
+    double x[{D}], P[{EE}];
+    rn::lds_to_regs<{D}>(s_x, lane, x);
+    rn::lds_to_regs<{EE}>(s_P, lane, P);
+    symmetrize_regs(P);
+    {ragged_note}
+    const int lc = lane < cnt ? lane : cnt - 1;
+    const bool live = lane < cnt;
+    double* zrow = gz + (base + lc) * {zmax};{sched_ptrs}
+    double cur[{K}][{zmax}], nxt[{K}][{zmax}]{decl_d};
+    int flb[{K}]{decl_i};{decl_more}
+    {issue.replace("TB_", "((int64_t)0)")}
+    for (int64_t tb = 0; tb < T; tb += {K}) {{
+      // everything in flight lands: this block's rows and schedule (and the stores issued one block ago)
+#pragma unroll
+      for (int u = 0; u < {K}; u++) {{
+#pragma unroll
+        for (int i = 0; i < {zmax}; i++) rn::pin(nxt[u][i]);{pin_row}
+      }}{pin_block}
+      if (tb > 0 && live) {{
+        double* yp_ = zrow + (tb - {K}) * rowstride;
+        uint8_t* fp_ = flags + (tb - {K}) * n + base + lane;
+#pragma unroll
+        for (int u = 0; u < {K}; u++) {{
+{store}
+        }}
+      }}
+#pragma unroll
+      for (int u = 0; u < {K}; u++) {{
+#pragma unroll
+        for (int i = 0; i < {zmax}; i++) cur[u][i] = nxt[u][i];{rot_row}
+      }}{rot_block}
+      {issue.replace("TB_", f"(tb + {K})")}
+#pragma unroll
+      for (int u = 0; u < {K}; u++) {{
+        const int64_t t = tb + u;
+        flb[u] = 0;
+        if (t < T) {{
+{step}
+          flb[u] = fl;{tstore}
+        }}
+      }}
+    }}
+    if (live) {{
+      const int64_t tl = ((T - 1) / {K}) * {K};          // first step of the last block
+      double* yp_ = zrow + tl * rowstride;
+      uint8_t* fp_ = flags + tl * n + base + lane;
+#pragma unroll
+      for (int u = 0; u < {K}; u++) {{
+        if (tl + u < T) {{
+{store}
+        }}
+      }}
+    }}{reload}
+{write_back}
+    rn::wave_lds_sync();
+    rn::tile_l2g<{D}>(gx + base * {D}, cnt, s_x, lane);
+    rn::tile_l2g<{EE}>(gP + base * {EE}, cnt, s_P, lane);
+    rn::wave_lds_sync();
+  }}
+}}
+"""
+
+
 def run_kernel_blk(spec, norm, trace=False):
   """The fused run without trace (tx == tP == nullptr), restructured around what the counters of k_run show for small models: the
   arithmetic of a step is tens of fp64 instructions, the step took thousands of cycles, because every step (a) waited for its own
@@ -759,18 +882,28 @@ def run_kernel_blk(spec, norm, trace=False):
 
   trace=True: the same structure writing the filtered trace -- every step's x / P leave through the LDS image as coalesced stores that
   nothing waits for until the next block starts (k_run_blk_tr; the step-at-a-time k_run paid a store wait per step: MI355X, same call,
-  8 192 x 200 kinematic6 3.04 -> 3.38 G steps/s, 65 536 x 200 kinematic 59 -> 75 G steps/s, results bit-identical)."""
-  D, E = spec.dim_x, spec.dim_err
-  EE = E * E
-  zmax = max(k.zdim for k in spec.kinds)
-  ZZ = zmax * zmax
+  8 192 x 200 kinematic6 3.04 -> 3.38 G steps/s, 65 536 x 200 kinematic 59 -> 75 G steps/s, results bit-identical).
+
+  The kernel's text is _blocked_run's; what is here is the shared schedule: fetched by the lanes, a step each, and broadcast when the step runs."""
+  ZZ = max(k.zdim for k in spec.kinds) ** 2
   K = run_block(spec)
   NR = (K * ZZ + 63) // 64
   cases = kind_cases(spec, "_regs_sym", "cur[u]", f"lane_bcast(Rv[(u * {ZZ} + i) >> 6], (u * {ZZ} + i) & 63)", ea_lane="lc", ind=10)
-  # rows are addressed by pointer increments (one 64-bit multiply per block, none per row): a row past the end of the schedule
-  # re-reads row T - 1 (the increment is zero there), so the loads stay unconditional
-  issue = f"""{{
-      const int64_t tb0_ = TB_ < T ? TB_ : T - 1;
+  return _blocked_run(
+    spec, norm, trace, K, kname="k_run_blk_tr" if trace else "k_run_blk",
+    title=(f"// ---- fused multi-step run with the filtered trace: blocks of {K} steps, no store is waited for inside a block -----------------"
+           if trace else
+           f"// ---- fused multi-step run without trace: blocks of {K} steps in registers (see emit_small.run_kernel_blk) -------------------"),
+    helpers="" if trace else """
+__device__ __forceinline__ double lane_bcast(const double v, const int l) {      // lane l's value in every lane (l uniform): two v_readlane_b32
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+__device__ __forceinline__ void pin_i(int& v) { asm volatile("" : "+v"(v)); }
+""",
+    args=",\n    const double* __restrict__ gea", unused="\n  (void)gea;",
+    ragged_note="// lanes past the end of a ragged tile compute on a copy of the last filter's rows and store nothing",
+    decl_d=f", Rv[{NR}], Rn[{NR}], dtv, dtn", decl_i=", kv, kn",
+    issue_sched=f"""
       const int64_t ts_ = TB_ + (lane < {K} ? lane : {K - 1});
       const int64_t tsc_ = ts_ < T ? ts_ : T - 1;
       dtn = dts[tsc_];
@@ -779,105 +912,18 @@ def run_kernel_blk(spec, norm, trace=False):
       for (int r = 0; r < {NR}; r++) {{           // R of the block's steps, flat: lane l of register r holds double r * 64 + l
         const int64_t ri_ = tb0_ * {ZZ} + r * 64 + lane;
         Rn[r] = gR[ri_ < T * {ZZ} ? ri_ : T * {ZZ} - 1];
-      }}
-      const double* zp_ = zrow + tb0_ * rowstride;
-      const int64_t left_ = T - 1 - tb0_;          // rows of the schedule after row tb0_
-#pragma unroll
-      for (int u = 0; u < {K}; u++) {{
-#pragma unroll
-        for (int i = 0; i < {zmax}; i++) nxt[u][i] = zp_[i];
-        zp_ += (u < left_) ? rowstride : 0;
-      }}
-    }}"""
-  store = f"""#pragma unroll
-          for (int i = 0; i < {zmax}; i++) yp_[i] = cur[u][i];
-          if (flags != nullptr) fp_[0] = (uint8_t)flb[u];
-          yp_ += rowstride;
-          fp_ += n;"""
-  helpers = "" if trace else """
-__device__ __forceinline__ double lane_bcast(const double v, const int l) {      // lane l's value in every lane (l uniform): two v_readlane_b32
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-__device__ __forceinline__ void pin_i(int& v) { asm volatile("" : "+v"(v)); }
-"""
-  title = (f"// ---- fused multi-step run with the filtered trace: blocks of {K} steps, no store is waited for inside a block -----------------"
-           if trace else
-           f"// ---- fused multi-step run without trace: blocks of {K} steps in registers (see emit_small.run_kernel_blk) -------------------")
-  kname = "k_run_blk_tr" if trace else "k_run_blk"
-  targs = ",\n    double* __restrict__ tx, double* __restrict__ tP" if trace else ""
-  tstore = f"""
-          // filtered pair of step t: through the LDS image, coalesced; the stores drain under the following steps
-          rn::regs_to_lds<{D}>(s_x, lane, x);
-          rn::regs_to_lds<{EE}>(s_P, lane, P);
-          rn::wave_lds_sync();
-          if (tx != nullptr) rn::tile_l2g<{D}>(tx + (t * n + base) * {D}, cnt, s_x, lane);
-          if (tP != nullptr) rn::tile_l2g<{EE}>(tP + (t * n + base) * {EE}, cnt, s_P, lane);
-          rn::wave_lds_sync();""" if trace else ""
-  return f"""{helpers}
-{title}
-__global__ __launch_bounds__(64) void {kname}(double* __restrict__ gx, double* __restrict__ gP, const double* __restrict__ gQ,
-    const int32_t* __restrict__ kinds, const double* __restrict__ dts, const int64_t T, double* gz,
-    const double* __restrict__ gR, const int64_t n, const int norm_quats, uint8_t* __restrict__ flags,
-    const double* __restrict__ gea{targs}) {{
-  (void)gea;
-{_lds(x=D, P=EE)}
-{_lds(True, Q=EE)}
-  const int lane = threadIdx.x;
-  for (int i = lane; i < {EE}; i += 64) s_Q[i] = gQ[i];
-  const int64_t tiles = (n + 63) >> 6;
-  const int64_t rowstride = n * {zmax};               // doubles between the rows of one filter in consecutive steps
-  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {{
-    const int64_t base = tile << 6;
-    const int cnt = (n - base) < 64 ? (int)(n - base) : 64;
-    rn::tile_g2l<{D}>(gx + base * {D}, cnt, s_x, lane);
-    rn::tile_g2l<{EE}>(gP + base * {EE}, cnt, s_P, lane);
-    rn::wave_lds_sync();
-    double x[{D}], P[{EE}];
-    rn::lds_to_regs<{D}>(s_x, lane, x);
-    rn::lds_to_regs<{EE}>(s_P, lane, P);
-    symmetrize_regs(P);
-    // lanes past the end of a ragged tile compute on a copy of the last filter's rows and store nothing
-    const int lc = lane < cnt ? lane : cnt - 1;
-    const bool live = lane < cnt;
-    double* zrow = gz + (base + lc) * {zmax};
-    double cur[{K}][{zmax}], nxt[{K}][{zmax}], Rv[{NR}], Rn[{NR}], dtv, dtn;
-    int flb[{K}], kv, kn;
-    {issue.replace("TB_", "((int64_t)0)")}
-    for (int64_t tb = 0; tb < T; tb += {K}) {{
-      // everything in flight lands: this block's rows and schedule (and the stores issued one block ago)
-#pragma unroll
-      for (int u = 0; u < {K}; u++) {{
-#pragma unroll
-        for (int i = 0; i < {zmax}; i++) rn::pin(nxt[u][i]);
-      }}
+      }}""",
+    pin_block=f"""
       rn::pin(dtn);
       pin_i(kn);
 #pragma unroll
-      for (int r = 0; r < {NR}; r++) rn::pin(Rn[r]);
-      if (tb > 0 && live) {{
-        double* yp_ = zrow + (tb - {K}) * rowstride;
-        uint8_t* fp_ = flags + (tb - {K}) * n + base + lane;
-#pragma unroll
-        for (int u = 0; u < {K}; u++) {{
-{store}
-        }}
-      }}
-#pragma unroll
-      for (int u = 0; u < {K}; u++) {{
-#pragma unroll
-        for (int i = 0; i < {zmax}; i++) cur[u][i] = nxt[u][i];
-      }}
+      for (int r = 0; r < {NR}; r++) rn::pin(Rn[r]);""",
+    rot_block=f"""
       dtv = dtn;
       kv = kn;
 #pragma unroll
-      for (int r = 0; r < {NR}; r++) Rv[r] = Rn[r];
-      {issue.replace("TB_", f"(tb + {K})")}
-#pragma unroll
-      for (int u = 0; u < {K}; u++) {{
-        const int64_t t = tb + u;
-        flb[u] = 0;
-        if (t < T) {{
-          const double dt = lane_bcast(dtv, u);
+      for (int r = 0; r < {NR}; r++) Rv[r] = Rn[r];""",
+    step=f"""          const double dt = lane_bcast(dtv, u);
           const int kind = __builtin_amdgcn_readlane(kv, u);
           predict_regs_sym(x, P, s_Q, dt);
           {norm}
@@ -886,31 +932,8 @@ __global__ __launch_bounds__(64) void {kname}(double* __restrict__ gx, double* _
 {cases}
             default: fl = 8; break;      // kind not available in the fused run (unknown, or it takes extra arguments)
           }}
-          {norm}
-          flb[u] = fl;{tstore}
-        }}
-      }}
-    }}
-    if (live) {{
-      const int64_t tl = ((T - 1) / {K}) * {K};          // first step of the last block
-      double* yp_ = zrow + tl * rowstride;
-      uint8_t* fp_ = flags + tl * n + base + lane;
-#pragma unroll
-      for (int u = 0; u < {K}; u++) {{
-        if (tl + u < T) {{
-{store}
-        }}
-      }}
-    }}
-    rn::regs_to_lds<{D}>(s_x, lane, x);
-    rn::regs_to_lds<{EE}>(s_P, lane, P);
-    rn::wave_lds_sync();
-    rn::tile_l2g<{D}>(gx + base * {D}, cnt, s_x, lane);
-    rn::tile_l2g<{EE}>(gP + base * {EE}, cnt, s_P, lane);
-    rn::wave_lds_sync();
-  }}
-}}
-"""
+          {norm}""",
+    trace_note="// filtered pair of step t: through the LDS image, coalesced; the stores drain under the following steps")
 
 
 def run_pf_block(spec):
@@ -928,122 +951,32 @@ def run_pf_kernel(spec, norm, trace=False):
   lane's registers and its z row stay as they are.  A filter without a stepped entry in the whole schedule is not written back: its lane
   leaves the LDS image as it was loaded (the `_masked` kernels' rule).
   trace=True: k_run_pf_tr, every step's pair of every filter (stepped or not: the trace is dense) leaves through the LDS image as in
-  k_run_blk_tr; the image of the final write-back is loaded again in front of it, since the trace has overwritten the one that came in."""
-  D, E = spec.dim_x, spec.dim_err
-  EE = E * E
-  zmax = max(k.zdim for k in spec.kinds)
-  ZZ = zmax * zmax
+  k_run_blk_tr; the image of the final write-back is loaded again in front of it, since the trace has overwritten the one that came in.
+
+  The kernel's text is _blocked_run's; what is here is the schedule per lane, a register per step of the block, the table of R and `stepped`."""
+  ZZ = max(k.zdim for k in spec.kinds) ** 2
   NK = len(spec.kinds)
   K = run_pf_block(spec)
   cases = kind_cases(spec, "_regs_sym", "cur[u]", lambda idx: f"s_R[{idx * ZZ} + i]", ind=12)
   known = " ".join(f"case {k.kind}:" for k in spec.kinds)
-  # rows are addressed by pointer increments as in k_run_blk: a row past the end of the schedule re-reads row T - 1
-  issue = f"""{{
-      const int64_t tb0_ = TB_ < T ? TB_ : T - 1;
-      const double* zp_ = zrow + tb0_ * rowstride;
-      const int32_t* kp_ = krow + tb0_ * n;
-      const double* dp_ = drow + tb0_ * n;
-      const int64_t left_ = T - 1 - tb0_;          // rows of the schedule after row tb0_
-#pragma unroll
-      for (int u = 0; u < {K}; u++) {{
-        kn[u] = kp_[0];
-        dtn[u] = dp_[0];
-#pragma unroll
-        for (int i = 0; i < {zmax}; i++) nxt[u][i] = zp_[i];
-        zp_ += (u < left_) ? rowstride : 0;
-        kp_ += (u < left_) ? n : 0;
-        dp_ += (u < left_) ? n : 0;
-      }}
-    }}"""
-  store = f"""#pragma unroll
-          for (int i = 0; i < {zmax}; i++) yp_[i] = cur[u][i];
-          if (flags != nullptr) fp_[0] = (uint8_t)flb[u];
-          yp_ += rowstride;
-          fp_ += n;"""
-  kname = "k_run_pf_tr" if trace else "k_run_pf"
-  title = (f"// ---- fused run, a schedule per filter, with the filtered trace: blocks of {K} steps (see emit_small.run_pf_kernel) ----------------"
+  return _blocked_run(
+    spec, norm, trace, K, kname="k_run_pf_tr" if trace else "k_run_pf",
+    title=(f"// ---- fused run, a schedule per filter, with the filtered trace: blocks of {K} steps (see emit_small.run_pf_kernel) ----------------"
            if trace else
-           f"// ---- fused run, a schedule per filter (kinds (T, n), dts (T, n)): blocks of {K} steps in registers (emit_small.run_pf_kernel) ----")
-  helpers = "" if trace else """
+           f"// ---- fused run, a schedule per filter (kinds (T, n), dts (T, n)): blocks of {K} steps in registers (emit_small.run_pf_kernel) ----"),
+    helpers="" if trace else """
 __device__ __forceinline__ void pin_k(int& v) { asm volatile("" : "+v"(v)); }
-"""
-  targs = ",\n    double* __restrict__ tx, double* __restrict__ tP" if trace else ""
-  tstore = f"""
-          // pair of every filter after step t (an idle filter's is the one it had): through the LDS image, coalesced
-          rn::regs_to_lds<{D}>(s_x, lane, x);
-          rn::regs_to_lds<{EE}>(s_P, lane, P);
-          rn::wave_lds_sync();
-          if (tx != nullptr) rn::tile_l2g<{D}>(tx + (t * n + base) * {D}, cnt, s_x, lane);
-          if (tP != nullptr) rn::tile_l2g<{EE}>(tP + (t * n + base) * {EE}, cnt, s_P, lane);
-          rn::wave_lds_sync();""" if trace else ""
-  reload = f"""
-    // the image the filters came with, again (the trace has overwritten it; x and P in HBM are still untouched)
-    rn::tile_g2l<{D}>(gx + base * {D}, cnt, s_x, lane);
-    rn::tile_g2l<{EE}>(gP + base * {EE}, cnt, s_P, lane);
-    rn::wave_lds_sync();""" if trace else ""
-  return f"""{helpers}
-{title}
-__global__ __launch_bounds__(64) void {kname}(double* __restrict__ gx, double* __restrict__ gP, const double* __restrict__ gQ,
-    const int32_t* __restrict__ kinds, const double* __restrict__ dts, const int64_t T, double* gz,
-    const double* __restrict__ gR, const int64_t n, const int norm_quats, uint8_t* __restrict__ flags{targs}) {{
-{_lds(x=D, P=EE)}
-{_lds(True, Q=EE, R=NK * ZZ)}
-  const int lane = threadIdx.x;
-  for (int i = lane; i < {EE}; i += 64) s_Q[i] = gQ[i];
-  for (int i = lane; i < {NK * ZZ}; i += 64) s_R[i] = gR[i];      // one row per kind, in the order of the model's kinds
-  const int64_t tiles = (n + 63) >> 6;
-  const int64_t rowstride = n * {zmax};               // doubles between the rows of one filter in consecutive steps
-  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {{
-    const int64_t base = tile << 6;
-    const int cnt = (n - base) < 64 ? (int)(n - base) : 64;
-    rn::tile_g2l<{D}>(gx + base * {D}, cnt, s_x, lane);
-    rn::tile_g2l<{EE}>(gP + base * {EE}, cnt, s_P, lane);
-    rn::wave_lds_sync();
-    double x[{D}], P[{EE}];
-    rn::lds_to_regs<{D}>(s_x, lane, x);
-    rn::lds_to_regs<{EE}>(s_P, lane, P);
-    symmetrize_regs(P);
-    // lanes past the end of a ragged tile follow a copy of the last filter's schedule and rows and store nothing
-    const int lc = lane < cnt ? lane : cnt - 1;
-    const bool live = lane < cnt;
-    double* zrow = gz + (base + lc) * {zmax};
-    const int32_t* krow = kinds + base + lc;
-    const double* drow = dts + base + lc;
-    double cur[{K}][{zmax}], nxt[{K}][{zmax}], dtv[{K}], dtn[{K}];
-    int flb[{K}], kv[{K}], kn[{K}];
-    bool stepped = false;
-    {issue.replace("TB_", "((int64_t)0)")}
-    for (int64_t tb = 0; tb < T; tb += {K}) {{
-      // everything in flight lands: this block's rows and schedule (and the stores issued one block ago)
-#pragma unroll
-      for (int u = 0; u < {K}; u++) {{
-#pragma unroll
-        for (int i = 0; i < {zmax}; i++) rn::pin(nxt[u][i]);
-        rn::pin(dtn[u]);
-        pin_k(kn[u]);
-      }}
-      if (tb > 0 && live) {{
-        double* yp_ = zrow + (tb - {K}) * rowstride;
-        uint8_t* fp_ = flags + (tb - {K}) * n + base + lane;
-#pragma unroll
-        for (int u = 0; u < {K}; u++) {{
-{store}
-        }}
-      }}
-#pragma unroll
-      for (int u = 0; u < {K}; u++) {{
-#pragma unroll
-        for (int i = 0; i < {zmax}; i++) cur[u][i] = nxt[u][i];
-        dtv[u] = dtn[u];
-        kv[u] = kn[u];
-      }}
-      {issue.replace("TB_", f"(tb + {K})")}
-#pragma unroll
-      for (int u = 0; u < {K}; u++) {{
-        const int64_t t = tb + u;
-        flb[u] = 0;
-        if (t < T) {{
-          const int kind = kv[u];
+""",
+    lds=dict(R=NK * ZZ), fill=f"\n  for (int i = lane; i < {NK * ZZ}; i += 64) s_R[i] = gR[i];      // one row per kind, in the order of the model's kinds",
+    ragged_note="// lanes past the end of a ragged tile follow a copy of the last filter's schedule and rows and store nothing",
+    sched_ptrs="\n    const int32_t* krow = kinds + base + lc;\n    const double* drow = dts + base + lc;",
+    decl_d=f", dtv[{K}], dtn[{K}]", decl_i=f", kv[{K}], kn[{K}]", decl_more="\n    bool stepped = false;",
+    # the schedule is addressed by pointer increments like the rows
+    issue_ptrs="\n      const int32_t* kp_ = krow + tb0_ * n;\n      const double* dp_ = drow + tb0_ * n;",
+    issue_row="\n        kn[u] = kp_[0];\n        dtn[u] = dp_[0];",
+    issue_step="\n        kp_ += (u < left_) ? n : 0;\n        dp_ += (u < left_) ? n : 0;",
+    pin_row="\n        rn::pin(dtn[u]);\n        pin_k(kn[u]);", rot_row="\n        dtv[u] = dtn[u];\n        kv[u] = kn[u];",
+    step=f"""          const int kind = kv[u];
           int fl = 16;                             // idle entry: no predict, the row passes through
           if (kind > 0) {{
             switch (kind) {{
@@ -1064,45 +997,27 @@ __global__ __launch_bounds__(64) void {kname}(double* __restrict__ gx, double* _
               default: break;
             }}
             {norm}
-          }}
-          flb[u] = fl;{tstore}
-        }}
-      }}
-    }}
-    if (live) {{
-      const int64_t tl = ((T - 1) / {K}) * {K};          // first step of the last block
-      double* yp_ = zrow + tl * rowstride;
-      uint8_t* fp_ = flags + tl * n + base + lane;
-#pragma unroll
-      for (int u = 0; u < {K}; u++) {{
-        if (tl + u < T) {{
-{store}
-        }}
-      }}
-    }}{reload}
-    // a filter that no entry of its schedule stepped keeps the record it came with: its lane does not touch the image
-    if (live && stepped) {{
-      rn::regs_to_lds<{D}>(s_x, lane, x);
-      rn::regs_to_lds<{EE}>(s_P, lane, P);
-    }}
-    rn::wave_lds_sync();
-    rn::tile_l2g<{D}>(gx + base * {D}, cnt, s_x, lane);
-    rn::tile_l2g<{EE}>(gP + base * {EE}, cnt, s_P, lane);
-    rn::wave_lds_sync();
-  }}
-}}
-"""
+          }}""",
+    trace_note="// pair of every filter after step t (an idle filter's is the one it had): through the LDS image, coalesced",
+    reload_note="// the image the filters came with, again (the trace has overwritten it; x and P in HBM are still untouched)",
+    wb_guard="    // a filter that no entry of its schedule stepped keeps the record it came with: its lane does not touch the image\n"
+             "    if (live && stepped)")
+
+
+def _launch_blocked(kname, more=""):
+  """Launch text of a blocked run: `kname` without a trace, `kname`_tr with one."""
+  return f"""  const int64_t tiles = (n + 63) >> 6;
+  if (trace_x == nullptr && trace_P == nullptr) {{
+    hipLaunchKernelGGL({kname}, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
+                       x, P, Q, kinds, dts, T, z, R, n, norm_quats, flags{more});
+  }} else {{
+    hipLaunchKernelGGL({kname}_tr, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
+                       x, P, Q, kinds, dts, T, z, R, n, norm_quats, flags{more}, trace_x, trace_P);
+  }}"""
 
 
 def launch_run_pf():
-  return """  const int64_t tiles = (n + 63) >> 6;
-  if (trace_x == nullptr && trace_P == nullptr) {
-    hipLaunchKernelGGL(k_run_pf, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
-                       x, P, Q, kinds, dts, T, z, R, n, norm_quats, flags);
-  } else {
-    hipLaunchKernelGGL(k_run_pf_tr, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
-                       x, P, Q, kinds, dts, T, z, R, n, norm_quats, flags, trace_x, trace_P);
-  }"""
+  return _launch_blocked("k_run_pf")
 
 
 def launch_run(spec=None):
@@ -1111,12 +1026,4 @@ def launch_run(spec=None):
     return """  const int64_t tiles = (n + 63) >> 6;
   hipLaunchKernelGGL(k_run, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
                      x, P, Q, kinds, dts, T, z, R, n, norm_quats, flags, trace_x, trace_P, ea, augment);"""
-  return """  (void)augment;
-  const int64_t tiles = (n + 63) >> 6;
-  if (trace_x == nullptr && trace_P == nullptr) {
-    hipLaunchKernelGGL(k_run_blk, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
-                       x, P, Q, kinds, dts, T, z, R, n, norm_quats, flags, ea);
-  } else {
-    hipLaunchKernelGGL(k_run_blk_tr, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
-                       x, P, Q, kinds, dts, T, z, R, n, norm_quats, flags, ea, trace_x, trace_P);
-  }"""
+  return "  (void)augment;\n" + _launch_blocked("k_run_blk", ", ea")

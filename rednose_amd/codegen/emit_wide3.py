@@ -28,6 +28,8 @@ test_gpu_random.py, test_gpu_msckf.py, test_gpu_fullsize.py bound it.  Measureme
 (The same layout for the step-granular entry points was built in round 2 and measured slower than the three-phase kernels of
 emit_wide2 -- one wavefront per SIMD cannot overlap its own HBM round trip; numbers in profiles/tuning_notes.md.)
 """
+import types
+
 from rednose_amd.codegen import emit_wide2 as w2, tuning
 from rednose_amd.codegen.emit_common import EADIM, SlotLayout, ea_count, ind, term, sum_terms
 
@@ -276,61 +278,217 @@ def kernels(spec, with_run=True):
   """Matrix-phase device functions + the fused multi-step kernel (the phase-1 / phase-3 functions are emit_wide2's, which must
   precede this text in the generated file).  with_run=False: only the layout constants -- the model's fused run is emit_run2's k_run2
   (the smoother emitters use these constants and emit their own functions)."""
-  from rednose_amd.codegen import emit_wide2 as w2
+  from rednose_amd.codegen import emit      # (emit imports this module)
   GL, R, FPW = layout(spec)
   scal_text, lay = w2.device_functions(spec, lay_cls=RunLayout, sfx="_r")
+  slot_note = "fused run: doubles per scalar slot" if with_run else "doubles per scalar slot of the single-wavefront layout"
+  consts = [f"constexpr int GLR = {GL};    // fused run: lanes per filter", f"constexpr int RPL = {R};    // rows of P per lane",
+            f"constexpr int FPWR = {FPW};   // filters per wavefront", f"constexpr int SLOT_R = {lay.SLOT};   // {slot_note}", ""]
+  # the fused run with a schedule per filter: predicated matrix phases + k_run_pf
+  pf = []
+  if emit.run_pf(spec):
+    pf = [predict_fn(spec, pf=True), predict_fn(spec, qdiag=True, pf=True)] + [update_fn(spec, k, pf=True) for k in spec.kinds] + [run_pf_kernel(spec)]
   if not with_run:
-    from rednose_amd.codegen import emit      # (emit imports this module)
     # the model's batch_run is emit_run2's k_run2; the fused run with a schedule per filter is this module's single-wavefront structure:
     # the scalar phases against RunLayout, the predicated matrix phases and k_run_pf follow the constants
-    pf = ["", scal_text, "", predict_fn(spec, pf=True), predict_fn(spec, qdiag=True, pf=True)] + [update_fn(spec, k, pf=True) for k in spec.kinds] + \
-         [run_pf_kernel(spec)] if emit.run_pf(spec) else []
-    return "\n".join([f"constexpr int GLR = {GL};    // fused run: lanes per filter", f"constexpr int RPL = {R};    // rows of P per lane",
-                      f"constexpr int FPWR = {FPW};   // filters per wavefront", f"constexpr int SLOT_R = {lay.SLOT};   // doubles per scalar slot of the single-wavefront layout", ""] + pf)
-  out = [f"constexpr int GLR = {GL};    // fused run: lanes per filter", f"constexpr int RPL = {R};    // rows of P per lane",
-         f"constexpr int FPWR = {FPW};   // filters per wavefront", f"constexpr int SLOT_R = {lay.SLOT};   // fused run: doubles per scalar slot",
-         "", scal_text, "", predict_fn(spec), predict_fn(spec, qdiag=True)]
-  for k in spec.kinds:
-    out.append(update_fn(spec, k))
-  out.append(run_kernel(spec))
-  from rednose_amd.codegen import emit      # (emit imports this module)
-  if emit.run_pf(spec):            # the fused run with a schedule per filter: predicated matrix phases + k_run_pf
-    out += [predict_fn(spec, pf=True), predict_fn(spec, qdiag=True, pf=True)] + [update_fn(spec, k, pf=True) for k in spec.kinds] + [run_pf_kernel(spec)]
-  return "\n".join(out)
+    return "\n".join(consts + (["", scal_text, ""] + pf if pf else []))
+  return "\n".join(consts + [scal_text, "", predict_fn(spec), predict_fn(spec, qdiag=True)] + [update_fn(spec, k) for k in spec.kinds] + [run_kernel(spec)] + pf)
 
 
-def run_kernel(spec):
+def _obs_fragments(lay, zmax, FPW, indexed, count_note):
+  """How the observations travel: the entries a lane carries between HBM and the slots, FPW * zmax values per tile and step, one per lane and
+  pass (a single pass up to 8-dimensional observations at 8 filters per wavefront; the reference puts no limit on ZDIM, ekf_c.c:37).
+  indexed=False (a single pass) prints the names without an index, zf / slz / zn, as k_run does; count_note: the comment behind the indexed
+  declaration."""
+  NZ = -(-(FPW * zmax) // 64)
+  z = types.SimpleNamespace()
+  if not indexed:
+    assert NZ == 1
+    z.decl = f"const int zf = lane / {zmax}, zc = lane % {zmax};                // observation entry this lane carries between HBM and the slots"
+    z.tile_a = "    const bool zlive = zf < cnt;\n"
+    z.tile_b = f"    double* slz = s_sl + (zlive ? zf : 0) * SLOT_R + {lay.OFF_Y} + zc;\n"
+    z.first = f"    if (zlive) *slz = gz[base * {zmax} + lane];"
+    z.next = ("      double zn = 0.0;                                 // next step's observation, in flight during this step\n"
+              f"      if (t + 1 < T && zlive) zn = gz[((t + 1) * n + base) * {zmax} + lane];")
+    z.out = f"      if (zlive) gz[(t * n + base) * {zmax} + lane] = *slz;          // y (the observation itself after an unknown kind)"
+    z.commit = "      if (zlive) *slz = zn;"
+    return z
+  q_ = range(NZ)
+  z.decl = " ".join(f"const int zf{q} = (lane + {64 * q}) / {zmax}, zc{q} = (lane + {64 * q}) % {zmax};" for q in q_) + \
+           (f"      // {NZ} observation entries per lane ({FPW} filters x {zmax})" if count_note else "")
+  z.tile_a = "".join(f"    const bool zlive{q} = zf{q} < cnt;\n" for q in q_)
+  z.tile_b = "".join(f"    double* slz{q} = s_sl + (zlive{q} ? zf{q} : 0) * SLOT_R + {lay.OFF_Y} + zc{q};\n" for q in q_)
+  z.first = "\n".join(f"    if (zlive{q}) *slz{q} = gz[base * {zmax} + lane + {64 * q}];" for q in q_)
+  z.next = "\n".join([f"      double zn[{NZ}] = {{{', '.join('0.0' for _ in q_)}}};                 // next step's observations, in flight during this step"] +
+                     [f"      if (t + 1 < T && zlive{q}) zn[{q}] = gz[((t + 1) * n + base) * {zmax} + lane + {64 * q}];" for q in q_])
+  z.out = "\n".join(f"      if (zlive{q}) gz[(t * n + base) * {zmax} + lane + {64 * q}] = *slz{q};" for q in q_)
+  z.commit = "\n".join(f"      if (zlive{q}) *slz{q} = zn[{q}];" for q in q_)
+  return z
+
+
+def _row_args(R):
+  """The register rows and their indices as call arguments."""
+  return ", ".join(f"row{s}" for s in range(R)), ", ".join(f"rr{s}, rc{s}, ok{s}" for s in range(R))
+
+
+def _img(E, R, cond=""):
+  """rows -> LDS image (only where something reads the image: trace, window shift, the final store)"""
+  return "\n".join(f"        if (ok{s}{cond}) {{\n#pragma unroll\n          for (int j = 0; j < {E}; j++) sP[rr{s} * {E} + j] = row{s}[j];\n        }}" for s in range(R))
+
+
+def _stamp(ph):
+  """A line of k_run with a debug stamp (tuning knob wide_timeline; tools/timeline.py run): the last three steps, twenty stamps each."""
+  if not tuning.current().wide_timeline:
+    return "\n      "
+  return (f"\n      if (lane == 0 && blockIdx.x < 256) {{ const int ti_ = (int)(t % 3) * 20 + {ph}; "
+          "g_tl[(blockIdx.x * 64 + ti_) * 2] = __builtin_readcyclecounter(); g_tl[(blockIdx.x * 64 + ti_) * 2 + 1] = wall_clock64(); }")
+
+
+def _fused_run(spec, pf, *, title, sched, update, flags_rule, args="", unused="", pre_loop="", after_step=""):
+  """The text of a single-wavefront fused run, once: kernel head, LDS, the tile prologue (images, slots, observations, rows into registers), the
+  step loop (predict, update, inject, y and the trace out, the next observation in) and the write-back.  `pf`: a schedule per filter (k_run_pf)
+  instead of a shared one (k_run) -- the predicates of the predict phase, the predicated matrix functions, the write-back into the image
+  loaded again, and without k_run's notes and debug stamps.  The keyword arguments are the text the two kernels do not share: title, trailing
+  arguments, what precedes the loop, the schedule fetch (through the predicates), the update's scalar and matrix dispatch, the flags rule
+  and what follows a step."""
   D, E = spec.dim_x, spec.dim_err
   EE = E * E
   GL, R, FPW = layout(spec)
   lay = w2.slot_tables(spec, RunLayout)[0]
   zmax = max(k.zdim for k in spec.kinds)
-  # observation entries a lane carries between HBM and the slots: FPW * zmax values per tile and step, one per lane and pass
-  # (a single pass up to 8-dimensional observations at 8 filters per wavefront; the reference puts no limit on ZDIM, ekf_c.c:37)
-  NZ = -(-(FPW * zmax) // 64)
-  if NZ == 1:
-    z_decl = f"const int zf = lane / {zmax}, zc = lane % {zmax};                // observation entry this lane carries between HBM and the slots"
-    z_tile_a = "    const bool zlive = zf < cnt;\n"
-    z_tile_b = f"    double* slz = s_sl + (zlive ? zf : 0) * SLOT_R + {lay.OFF_Y} + zc;\n"
-    z_first = f"    if (zlive) *slz = gz[base * {zmax} + lane];"
-    z_next = ("      double zn = 0.0;                                 // next step's observation, in flight during this step\n"
-              f"      if (t + 1 < T && zlive) zn = gz[((t + 1) * n + base) * {zmax} + lane];")
-    z_out = f"      if (zlive) gz[(t * n + base) * {zmax} + lane] = *slz;          // y (the observation itself after an unknown kind)"
-    z_commit = "      if (zlive) *slz = zn;"
+  z = _obs_fragments(lay, zmax, FPW, indexed=pf or FPW * zmax > 64, count_note=not pf)
+  rows, idx = _row_args(R)
+  img = _img(E, R)
+  nt_trace = "true" if tuning.current().nt_trace else "false"
+  qd_decl = "\n".join(f"  const double qd{s} = gQ[((c + {GL * s}) < {E} ? (c + {GL * s}) : 0) * {E + 1}];" for s in range(R))
+  qd_args = ", ".join(f"qd{s}" for s in range(R))
+  decl_rows = "\n".join(f"    double row{s}[{E}];" for s in range(R))
+  decl_idx = "\n".join(f"    const int rr{s} = c + {GL * s}; const bool ok{s} = live && rr{s} < {E}; const int rc{s} = rr{s} < {E} ? rr{s} : 0;" for s in range(R))
+  # the fused run's covariance is symmetric by contract (include/rednose_amd_filter.h): (P + P^T) / 2 of the caller's matrix, once, as
+  # the rows enter the registers -- predict_fn / update_fn use P = P^T, the reference's dense products use both halves
+  load_rows = "\n".join(f"#pragma unroll\n    for (int j = 0; j < {E}; j++) row{s}[j] = 0.5 * (sP[rc{s} * {E} + j] + sP[j * {E} + rc{s}]);" for s in range(R))
+
+  def copy_in(l):
+    return f"    rn::copy_g2l<FPWR * {EE}>(gP + base * {EE}, cnt * {EE}, s_P, {l});"
+
+  def note(text):      # k_run's remarks; k_run_pf refers to k_run
+    return "" if pf else text
+  stamp = (lambda ph: "") if pf else _stamp
+  step, pd, any_pd, fsfx, pda = ("step", "pd", "__any(pd)", "_pf", ", pd") if pf else ("live", "do_pred", "do_pred", "", "")
+  le_decl = f"""    int le = lane;
+    asm volatile("" : "+v"(le));{note("         // (same: nothing of the first copy's index arithmetic is kept alive across the step loop)")}
+"""
+  if pf:      # a filter that no entry stepped is not written back: the image that came in, again, and only the groups that stepped put their rows into it
+    write_back = f"""    // the image the filters came with, again: a filter that no entry stepped leaves as it came (x: its slot was never written)
+{le_decl}{copy_in("le")}
+    rn::wave_lds_sync();
+{_img(E, R, " && stepped")}
+    rn::wave_lds_sync();
+"""
   else:
-    q_ = range(NZ)
-    z_decl = " ".join(f"const int zf{q} = (lane + {64 * q}) / {zmax}, zc{q} = (lane + {64 * q}) % {zmax};" for q in q_) + \
-             f"      // {NZ} observation entries per lane ({FPW} filters x {zmax})"
-    z_tile_a = "".join(f"    const bool zlive{q} = zf{q} < cnt;\n" for q in q_)
-    z_tile_b = "".join(f"    double* slz{q} = s_sl + (zlive{q} ? zf{q} : 0) * SLOT_R + {lay.OFF_Y} + zc{q};\n" for q in q_)
-    z_first = "\n".join(f"    if (zlive{q}) *slz{q} = gz[base * {zmax} + lane + {64 * q}];" for q in q_)
-    z_next = "\n".join([f"      double zn[{NZ}] = {{{', '.join('0.0' for _ in q_)}}};                 // next step's observations, in flight during this step"] +
-                        [f"      if (t + 1 < T && zlive{q}) zn[{q}] = gz[((t + 1) * n + base) * {zmax} + lane + {64 * q}];" for q in q_])
-    z_out = "\n".join(f"      if (zlive{q}) gz[(t * n + base) * {zmax} + lane + {64 * q}] = *slz{q};" for q in q_)
-    z_commit = "\n".join(f"      if (zlive{q}) *slz{q} = zn[{q}];" for q in q_)
+    write_back = f"""{img}
+    rn::wave_lds_sync();
+{le_decl}"""
+  # (Measured and not kept, round 4: the trace straight from the register rows as 8-byte stores to the TRANSPOSED positions -- lane c of
+  # a group holds P[c + GL s][j]; written to [j][c + GL s] the lanes of a group cover 64 contiguous bytes per instruction, no LDS image,
+  # no read-back -- config 4 forward 70.6 ms per chunk against 22.6 ms through the image: 66 store instructions per lane and step, each
+  # a scatter of eight 64-byte pieces.  Round 3 measured the row-wise 16-byte variant at 25.3 ms.  profiles/tuning_notes.md.)
+  # (Measured and not kept, round 4, profiles/tuning_notes.md: the copy of a step's covariance trace DEFERRED into the next step and woven
+  # between the statements of its scalar phase when that step has no predict -- LDS / store throughput under a chain of dependent fp64
+  # instructions, the arithmetic run redundantly on all lanes so that no divergent region separates the two streams.  Host-verified,
+  # parity-green on the device, and 8 % SLOWER: config 4 forward 23.6 ms per chunk against 21.8.)
+  return f"""
+{title}
+__global__ __launch_bounds__(64) void {"k_run_pf" if pf else "k_run"}(double* __restrict__ gx, double* __restrict__ gP, const double* __restrict__ gQ,
+    const int32_t* __restrict__ kinds, const double* __restrict__ dts, const int64_t T, double* __restrict__ gz,
+    const double* __restrict__ gR, const int64_t n, const int norm_quats, uint8_t* __restrict__ flags,
+    double* __restrict__ tx, double* __restrict__ tP{args}) {{{unused}
+  __shared__ __attribute__((aligned(16))) double s_P[FPWR * {EE} + 2];      // one image of P per filter{note(" (see emit_wide3.py)")}
+  __shared__ __attribute__((aligned(16))) double s_G[FPWR * {zmax * E}];     // G, then K^T
+  __shared__ __attribute__((aligned(16))) double s_sl[FPWR * SLOT_R];
+  const int lane = threadIdx.x;
+  const int g = lane / GLR;
+  const int c = lane % GLR;
+  {z.decl}{note(chr(10) + "  // a diagonal process noise (the usual case) lives in registers: see predict_fn(qdiag=True)")}
+  int qoff = 0;
+  for (int i = lane; i < {EE}; i += 64) qoff |= (i / {E} != i % {E}) && (gQ[i] != 0.0);
+  const bool qdiag = !__any(qoff);
+{qd_decl}
+  const int64_t tiles = (n + FPWR - 1) / FPWR;
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {{
+    const int64_t base = tile * FPWR;
+    const int cnt = (n - base) < FPWR ? (int)(n - base) : FPWR;
+    const int gg = g < cnt ? g : 0;
+    const bool live = g < cnt;
+{z.tile_a}    double* sP = s_P + gg * {EE};
+    double* sl = s_sl + gg * SLOT_R;
+{z.tile_b}{decl_idx}
+    int lb = lane;
+    asm volatile("" : "+v"(lb));{note("         // opaque copy of the lane index: the copies' index arithmetic stays inside the tile")}
+{copy_in("lb")}
+    for (int i = lane; i < cnt * {D}; i += 64) s_sl[(i / {D}) * SLOT_R + {lay.OFF_X} + i % {D}] = gx[base * {D} + i];
+{z.first}
+    rn::wave_lds_sync();
+{decl_rows}
+{load_rows}
+{pre_loop}    for (int64_t t = 0; t < T; t++) {{
+{z.next}
+{sched}
+      // ---- phase 1a / 2a: predict{", per group on its own dt" if pf else ""} ----
+      if (c == 0 && {step}) {{
+        if ({pd}) scal_predict_r(sl + {lay.OFF_X}, dt, sl, norm_quats);
+        else scal_keep_r(sl + {lay.OFF_X}, sl, norm_quats);                 // predict(dt = 0) still renormalises
+      }}
+      rn::wave_lds_sync();{stamp(1)}
+      if ({any_pd}) {{
+        if (qdiag) {{
+          predict_rows_qd{fsfx}({rows}, sP, {qd_args}, sl, {idx}{pda}{_tl_arg(True)});
+        }} else {{
+          int qz = 0;
+          asm volatile("" : "+v"(qz));{note("                 // Q behind an opaque zero: its addresses are not worth registers across the step loop")}
+          predict_rows{fsfx}({rows}, sP, gQ + qz, sl, {idx}{pda}{_tl_arg(True)});
+        }}
+      }}{stamp(2)}
+      // ---- phase 1b / 2b: update{", every kind present among the wavefront's filters" if pf else ""} ----
+{update}{stamp(4)}
+      // ---- phase 3: lane 0 of each group injects the error state ----
+      if (c == 0 && live) {{
+{flags_rule}
+        if (flags != nullptr) flags[t * n + base + g] = (uint8_t)fl;
+      }}
+      rn::wave_lds_sync();{stamp(5)}
+{z.out}
+      int lz = lane;
+      asm volatile("" : "+v"(lz));{note("       // the copies' per-iteration indices are not worth registers across the step loop")}
+      if (tx != nullptr) {{
+        for (int i = lz; i < cnt * {D}; i += 64) tx[(t * n + base) * {D} + i] = s_sl[(i / {D}) * SLOT_R + {lay.OFF_X} + i % {D}];
+      }}
+      if (tP != nullptr) {{
+{img}
+        rn::wave_lds_sync();
+        rn::copy_l2g<FPWR * {EE}, {nt_trace}>(tP + (t * n + base) * {EE}, cnt * {EE}, s_P, lz);
+      }}
+      rn::wave_lds_sync();{stamp(6)}
+{z.commit}
+      rn::wave_lds_sync();{stamp(7)}{after_step}
+    }}
+{write_back}    rn::copy_l2g<FPWR * {EE}>(gP + base * {EE}, cnt * {EE}, s_P, le);
+    for (int i = le; i < cnt * {D}; i += 64) gx[base * {D} + i] = s_sl[(i / {D}) * SLOT_R + {lay.OFF_X} + i % {D}];
+    rn::wave_lds_sync();
+  }}
+}}
+"""
+
+
+def run_kernel(spec):
+  """k_run: the schedule is shared, kinds[t] and dts[t] are wave-uniform, and so is every branch of a step.  Extra arguments, feature-track
+  kinds and the MSCKF window shift exist here only (_fused_run holds the kernel's text)."""
+  D, E = spec.dim_x, spec.dim_err
+  _, R, _ = layout(spec)
+  lay = w2.slot_tables(spec, RunLayout)[0]
+  zmax = max(k.zdim for k in spec.kinds)
   EAM = ea_max(spec)
-  rows = ", ".join(f"row{s}" for s in range(R))
-  idx = ", ".join(f"rr{s}, rc{s}, ok{s}" for s in range(R))
+  rows, idx = _row_args(R)
   scal_cases, mat_cases = [], []
   for k in spec.kinds:
     EA = ea_count(k)
@@ -344,8 +502,6 @@ def run_kernel(spec):
       args += f", gR + t * {zmax * zmax}"
     scal_cases.append(f"          case {k.kind}: {{ {guard}scal_obs_{k.kind}_r{'<true>' if feat else ''}({args}); break; }}")
     mat_cases.append(f"        case {k.kind}: update_{k.kind}_rows({rows}, gR + t * {zmax * zmax}, sP, s_G + gg * {zmax * E}, sl, sl, {idx}{_tl_arg(True)}); break;")
-  # rows -> LDS image (only where something reads the image: trace, window shift, the final store)
-  img = "\n".join(f"        if (ok{s}) {{\n#pragma unroll\n          for (int j = 0; j < {E}; j++) sP[rr{s} * {E} + j] = row{s}[j];\n        }}" for s in range(R))
   aug = ""
   if spec.N > 0:
     d1, d2, d3, d4 = spec.dim_main, spec.dim_main_err, spec.dim_augment, spec.dim_augment_err
@@ -365,7 +521,7 @@ def run_kernel(spec):
       // of the state (one lane per filter) and of the rows / columns of P, read out of the LDS image (the trace above holds the
       // estimate BEFORE the shift, like the reference's Estimate)
       if (augs != nullptr && augs[t] != 0) {{
-{img}
+{_img(E, R)}
         rn::wave_lds_sync();
         if (c == 0 && live) {{
           double xo[{D}];
@@ -378,148 +534,35 @@ def run_kernel(spec):
       }}"""
   # predict(dt = 0) is skipped only for models where it is symbolically the identity (FilterSpec.identity_at_dt0)
   id0_guard = "true" if not spec.identity_at_dt0() else "dt != 0.0"
-  nt_trace = "true" if tuning.current().nt_trace else "false"
-  qd_decl = "\n".join(f"  const double qd{s} = gQ[((c + {GL * s}) < {E} ? (c + {GL * s}) : 0) * {E + 1}];" for s in range(R))
-  qd_args = ", ".join(f"qd{s}" for s in range(R))
-  decl_rows = "\n".join(f"    double row{s}[{E}];" for s in range(R))
-  decl_idx = "\n".join(f"    const int rr{s} = c + {GL * s}; const bool ok{s} = live && rr{s} < {E}; const int rc{s} = rr{s} < {E} ? rr{s} : 0;" for s in range(R))
-  # the fused run's covariance is symmetric by contract (include/rednose_amd_filter.h): (P + P^T) / 2 of the caller's matrix, once, as
-  # the rows enter the registers -- predict_fn / update_fn below use P = P^T, the reference's dense products use both halves
-  load_rows = "\n".join(f"#pragma unroll\n    for (int j = 0; j < {E}; j++) row{s}[j] = 0.5 * (sP[rc{s} * {E} + j] + sP[j * {E} + rc{s}]);" for s in range(R))
   nlc = chr(10)
-
-  def TL(ph):      # debug stamps (tuning knob wide_timeline; tools/timeline.py run): the last three steps, twenty stamps each
-    if not tuning.current().wide_timeline:
-      return ""
-    return (f"if (lane == 0 && blockIdx.x < 256) {{ const int ti_ = (int)(t % 3) * 20 + {ph}; "
-            "g_tl[(blockIdx.x * 64 + ti_) * 2] = __builtin_readcyclecounter(); g_tl[(blockIdx.x * 64 + ti_) * 2 + 1] = wall_clock64(); }")
-  # (Measured and not kept, round 4: the trace straight from the register rows as 8-byte stores to the TRANSPOSED positions -- lane c of
-  # a group holds P[c + GL s][j]; written to [j][c + GL s] the lanes of a group cover 64 contiguous bytes per instruction, no LDS image,
-  # no read-back -- config 4 forward 70.6 ms per chunk against 22.6 ms through the image: 66 store instructions per lane and step, each
-  # a scatter of eight 64-byte pieces.  Round 3 measured the row-wise 16-byte variant at 25.3 ms.  profiles/tuning_notes.md.)
-  # (Measured and not kept, round 4, profiles/tuning_notes.md: the copy of a step's covariance trace DEFERRED into the next step and woven
-  # between the statements of its scalar phase when that step has no predict -- LDS / store throughput under a chain of dependent fp64
-  # instructions, the arithmetic run redundantly on all lanes so that no divergent region separates the two streams.  Host-verified,
-  # parity-green on the device, and 8 % SLOWER: config 4 forward 23.6 ms per chunk against 21.8.)
-  scal_phase = f"""      if (c == 0 && live) {{
+  return _fused_run(
+    spec, False, title=f"""// ---- fused multi-step run: kinds[t], dts[t] shared by all filters; z is (T, n, {zmax}) in: z, out: y -----------
+// Per step, with P in registers: (1a) one lane per filter evaluates f and the non-trivial entries of F into the filter's LDS
+// slot, (2a) all lanes run predict's covariance algebra on their rows, (1b) one lane per filter evaluates h and He for the
+// observation kind, (2b) all lanes run the update's covariance algebra, (3) one lane per filter injects the error state.
+// x lives in the slot between the phases.""",
+    args=", const double* __restrict__ gea, const int32_t* __restrict__ augs", unused="\n  (void)gea; (void)augs;",
+    sched=f"""      const int kind = kinds[t];
+      const double dt = dts[t];
+      const bool do_pred = {id0_guard};{_stamp(0)}""",
+    update=f"""      int bad = 0;
+      if (c == 0 && live) {{
         switch (kind) {{
 {nlc.join(scal_cases)}
           default: bad = 8; break;      // unknown kind
         }}
-      }}"""
-  pend_decl = flush_before_predict = flush_after_loop = ""
-  trace_store = f"""{img}
-        rn::wave_lds_sync();
-        rn::copy_l2g<FPWR * {EE}, {nt_trace}>(tP + (t * n + base) * {EE}, cnt * {EE}, s_P, lz);"""
-  return f"""
-// ---- fused multi-step run: kinds[t], dts[t] shared by all filters; z is (T, n, {zmax}) in: z, out: y -----------
-// Per step, with P in registers: (1a) one lane per filter evaluates f and the non-trivial entries of F into the filter's LDS
-// slot, (2a) all lanes run predict's covariance algebra on their rows, (1b) one lane per filter evaluates h and He for the
-// observation kind, (2b) all lanes run the update's covariance algebra, (3) one lane per filter injects the error state.
-// x lives in the slot between the phases.
-__global__ __launch_bounds__(64) void k_run(double* __restrict__ gx, double* __restrict__ gP, const double* __restrict__ gQ,
-    const int32_t* __restrict__ kinds, const double* __restrict__ dts, const int64_t T, double* __restrict__ gz,
-    const double* __restrict__ gR, const int64_t n, const int norm_quats, uint8_t* __restrict__ flags,
-    double* __restrict__ tx, double* __restrict__ tP, const double* __restrict__ gea, const int32_t* __restrict__ augs) {{
-  (void)gea; (void)augs;
-  __shared__ __attribute__((aligned(16))) double s_P[FPWR * {EE} + 2];      // one image of P per filter (see emit_wide3.py)
-  __shared__ __attribute__((aligned(16))) double s_G[FPWR * {zmax * E}];     // G, then K^T
-  __shared__ __attribute__((aligned(16))) double s_sl[FPWR * SLOT_R];
-  const int lane = threadIdx.x;
-  const int g = lane / GLR;
-  const int c = lane % GLR;
-  {z_decl}
-  // a diagonal process noise (the usual case) lives in registers: see predict_fn(qdiag=True)
-  int qoff = 0;
-  for (int i = lane; i < {EE}; i += 64) qoff |= (i / {E} != i % {E}) && (gQ[i] != 0.0);
-  const bool qdiag = !__any(qoff);
-{qd_decl}
-  const int64_t tiles = (n + FPWR - 1) / FPWR;
-  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {{
-    const int64_t base = tile * FPWR;
-    const int cnt = (n - base) < FPWR ? (int)(n - base) : FPWR;
-    const int gg = g < cnt ? g : 0;
-    const bool live = g < cnt;
-{z_tile_a}    double* sP = s_P + gg * {EE};
-    double* sl = s_sl + gg * SLOT_R;
-{z_tile_b}{decl_idx}
-    int lb = lane;
-    asm volatile("" : "+v"(lb));         // opaque copy of the lane index: the copies' index arithmetic stays inside the tile
-    rn::copy_g2l<FPWR * {EE}>(gP + base * {EE}, cnt * {EE}, s_P, lb);
-    for (int i = lane; i < cnt * {D}; i += 64) s_sl[(i / {D}) * SLOT_R + {lay.OFF_X} + i % {D}] = gx[base * {D} + i];
-{z_first}
-    rn::wave_lds_sync();
-{decl_rows}
-{load_rows}
-{pend_decl}    for (int64_t t = 0; t < T; t++) {{
-{z_next}
-      const int kind = kinds[t];
-      const double dt = dts[t];
-      const bool do_pred = {id0_guard};
-      {TL(0)}
-      // ---- phase 1a / 2a: predict ----
-      if (c == 0 && live) {{
-        if (do_pred) scal_predict_r(sl + {lay.OFF_X}, dt, sl, norm_quats);
-        else scal_keep_r(sl + {lay.OFF_X}, sl, norm_quats);                 // predict(dt = 0) still renormalises
       }}
-      rn::wave_lds_sync();
-      {TL(1)}
-      if (do_pred) {{
-{flush_before_predict}        if (qdiag) {{
-          predict_rows_qd({rows}, sP, {qd_args}, sl, {idx}{_tl_arg(True)});
-        }} else {{
-          int qz = 0;
-          asm volatile("" : "+v"(qz));                 // Q behind an opaque zero: its addresses are not worth registers across the step loop
-          predict_rows({rows}, sP, gQ + qz, sl, {idx}{_tl_arg(True)});
-        }}
-      }}
-      {TL(2)}
-      // ---- phase 1b / 2b: update ----
-      int bad = 0;
-{scal_phase}
       bad = __builtin_amdgcn_readfirstlane(__any(bad) ? 8 : 0);
-      rn::wave_lds_sync();
-      {TL(3)}
+      rn::wave_lds_sync();{_stamp(3)}
       if (!bad) {{
         switch (kind) {{
 {nlc.join(mat_cases)}
           default: break;
         }}
-      }}
-      {TL(4)}
-      // ---- phase 3: lane 0 of each group injects the error state ----
-      if (c == 0 && live) {{
-        int fl = bad;
-        if (!bad) fl = scal_inject_r(sl, sl + {lay.OFF_X}, norm_quats) | (int)sl[{lay.OFF_FL}];
-        if (flags != nullptr) flags[t * n + base + g] = (uint8_t)fl;
-      }}
-      rn::wave_lds_sync();
-      {TL(5)}
-{z_out}
-      int lz = lane;
-      asm volatile("" : "+v"(lz));       // the copies' per-iteration indices are not worth registers across the step loop
-      if (tx != nullptr) {{
-        for (int i = lz; i < cnt * {D}; i += 64) tx[(t * n + base) * {D} + i] = s_sl[(i / {D}) * SLOT_R + {lay.OFF_X} + i % {D}];
-      }}
-      if (tP != nullptr) {{
-{trace_store}
-      }}
-      rn::wave_lds_sync();
-      {TL(6)}
-{z_commit}
-      rn::wave_lds_sync();
-      {TL(7)}{aug}
-    }}
-{flush_after_loop}{img}
-    rn::wave_lds_sync();
-    int le = lane;
-    asm volatile("" : "+v"(le));         // (same: nothing of the first copy's index arithmetic is kept alive across the step loop)
-    rn::copy_l2g<FPWR * {EE}>(gP + base * {EE}, cnt * {EE}, s_P, le);
-    for (int i = le; i < cnt * {D}; i += 64) gx[base * {D} + i] = s_sl[(i / {D}) * SLOT_R + {lay.OFF_X} + i % {D}];
-    rn::wave_lds_sync();
-  }}
-}}
-"""
+      }}""",
+    flags_rule=f"""        int fl = bad;
+        if (!bad) fl = scal_inject_r(sl, sl + {lay.OFF_X}, norm_quats) | (int)sl[{lay.OFF_FL}];""",
+    after_step=aug)
 
 
 def run_pf_kernel(spec):
@@ -530,25 +573,14 @@ def run_pf_kernel(spec):
   kind present among the wavefront's filters (a wave-uniform test) that kind's rows update runs on all lanes, changing the rows of the
   groups that carry it.  An idle group (kind <= 0, flag 16) and a group whose kind the model does not have (flag 8) keep slot and rows.
   A filter that no entry stepped is not written back: the image of the final store is the one that came in, loaded again, and only the
-  groups that stepped put their rows into it.  Above 32 error states a filter owns the wavefront and the tests are uniform anyway."""
-  D, E = spec.dim_x, spec.dim_err
-  EE = E * E
-  GL, R, FPW = layout(spec)
+  groups that stepped put their rows into it.  Above 32 error states a filter owns the wavefront and the tests are uniform anyway.
+  (_fused_run holds the kernel's text.)"""
+  E = spec.dim_err
+  _, R, _ = layout(spec)
   lay = w2.slot_tables(spec, RunLayout)[0]
   zmax = max(k.zdim for k in spec.kinds)
   ZZ = zmax * zmax
-  NZ = -(-(FPW * zmax) // 64)
-  q_ = range(NZ)
-  z_decl = " ".join(f"const int zf{q} = (lane + {64 * q}) / {zmax}, zc{q} = (lane + {64 * q}) % {zmax};" for q in q_)
-  z_tile_a = "".join(f"    const bool zlive{q} = zf{q} < cnt;\n" for q in q_)
-  z_tile_b = "".join(f"    double* slz{q} = s_sl + (zlive{q} ? zf{q} : 0) * SLOT_R + {lay.OFF_Y} + zc{q};\n" for q in q_)
-  z_first = "\n".join(f"    if (zlive{q}) *slz{q} = gz[base * {zmax} + lane + {64 * q}];" for q in q_)
-  z_next = "\n".join([f"      double zn[{NZ}] = {{{', '.join('0.0' for _ in q_)}}};                 // next step's observations, in flight during this step"] +
-                     [f"      if (t + 1 < T && zlive{q}) zn[{q}] = gz[((t + 1) * n + base) * {zmax} + lane + {64 * q}];" for q in q_])
-  z_out = "\n".join(f"      if (zlive{q}) gz[(t * n + base) * {zmax} + lane + {64 * q}] = *slz{q};" for q in q_)
-  z_commit = "\n".join(f"      if (zlive{q}) *slz{q} = zn[{q}];" for q in q_)
-  rows = ", ".join(f"row{s}" for s in range(R))
-  idx = ", ".join(f"rr{s}, rc{s}, ok{s}" for s in range(R))
+  rows, idx = _row_args(R)
   nlc = chr(10)
   known = " ".join(f"case {k.kind}:" for k in spec.kinds)
   scal_cases = nlc.join(f"          case {k.kind}: scal_obs_{k.kind}_r(sl, sl + {lay.OFF_Y}); break;" for k in spec.kinds)
@@ -556,58 +588,16 @@ def run_pf_kernel(spec):
         const bool mine = step && kind == {k.kind};
         if (__any(mine)) update_{k.kind}_rows_pf({rows}, gR + {i * ZZ}, sP, s_G + gg * {zmax * E}, sl, sl, {idx}, mine{_tl_arg(True)});
       }}""" for i, k in enumerate(spec.kinds))
-
-  def img(cond):
-    return "\n".join(f"        if (ok{s}{cond}) {{\n#pragma unroll\n          for (int j = 0; j < {E}; j++) sP[rr{s} * {E} + j] = row{s}[j];\n        }}" for s in range(R))
   id0_guard = "true" if not spec.identity_at_dt0() else "dt != 0.0"
-  nt_trace = "true" if tuning.current().nt_trace else "false"
-  qd_decl = "\n".join(f"  const double qd{s} = gQ[((c + {GL * s}) < {E} ? (c + {GL * s}) : 0) * {E + 1}];" for s in range(R))
-  qd_args = ", ".join(f"qd{s}" for s in range(R))
-  decl_rows = "\n".join(f"    double row{s}[{E}];" for s in range(R))
-  decl_idx = "\n".join(f"    const int rr{s} = c + {GL * s}; const bool ok{s} = live && rr{s} < {E}; const int rc{s} = rr{s} < {E} ? rr{s} : 0;" for s in range(R))
-  load_rows = "\n".join(f"#pragma unroll\n    for (int j = 0; j < {E}; j++) row{s}[j] = 0.5 * (sP[rc{s} * {E} + j] + sP[j * {E} + rc{s}]);" for s in range(R))
-  return f"""
-// ---- fused multi-step run, a schedule per filter: kinds (T, n), dts (T, n); z is (T, n, {zmax}) in: z, out: y; gR one row per kind -----------
-// k_run's phases per step; a group takes part in those its own entry asks for (see emit_wide3.run_pf_kernel).
-__global__ __launch_bounds__(64) void k_run_pf(double* __restrict__ gx, double* __restrict__ gP, const double* __restrict__ gQ,
-    const int32_t* __restrict__ kinds, const double* __restrict__ dts, const int64_t T, double* __restrict__ gz,
-    const double* __restrict__ gR, const int64_t n, const int norm_quats, uint8_t* __restrict__ flags,
-    double* __restrict__ tx, double* __restrict__ tP) {{
-  __shared__ __attribute__((aligned(16))) double s_P[FPWR * {EE} + 2];      // one image of P per filter
-  __shared__ __attribute__((aligned(16))) double s_G[FPWR * {zmax * E}];     // G, then K^T
-  __shared__ __attribute__((aligned(16))) double s_sl[FPWR * SLOT_R];
-  const int lane = threadIdx.x;
-  const int g = lane / GLR;
-  const int c = lane % GLR;
-  {z_decl}
-  int qoff = 0;
-  for (int i = lane; i < {EE}; i += 64) qoff |= (i / {E} != i % {E}) && (gQ[i] != 0.0);
-  const bool qdiag = !__any(qoff);
-{qd_decl}
-  const int64_t tiles = (n + FPWR - 1) / FPWR;
-  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {{
-    const int64_t base = tile * FPWR;
-    const int cnt = (n - base) < FPWR ? (int)(n - base) : FPWR;
-    const int gg = g < cnt ? g : 0;
-    const bool live = g < cnt;
-{z_tile_a}    double* sP = s_P + gg * {EE};
-    double* sl = s_sl + gg * SLOT_R;
-{z_tile_b}{decl_idx}
-    int lb = lane;
-    asm volatile("" : "+v"(lb));
-    rn::copy_g2l<FPWR * {EE}>(gP + base * {EE}, cnt * {EE}, s_P, lb);
-    for (int i = lane; i < cnt * {D}; i += 64) s_sl[(i / {D}) * SLOT_R + {lay.OFF_X} + i % {D}] = gx[base * {D} + i];
-{z_first}
-    rn::wave_lds_sync();
-{decl_rows}
-{load_rows}
-    bool stepped = false;
+  return _fused_run(
+    spec, True, title=f"""// ---- fused multi-step run, a schedule per filter: kinds (T, n), dts (T, n); z is (T, n, {zmax}) in: z, out: y; gR one row per kind -----------
+// k_run's phases per step; a group takes part in those its own entry asks for (see emit_wide3.run_pf_kernel).""",
+    pre_loop="""    bool stepped = false;
     // the group's own schedule entry, a step ahead (every lane of a group reads its filter's: one address per group)
     int kind_n = kinds[base + gg];
     double dt_n = dts[base + gg];
-    for (int64_t t = 0; t < T; t++) {{
-{z_next}
-      const int kind = live ? kind_n : 0;
+""",
+    sched=f"""      const int kind = live ? kind_n : 0;
       const double dt = dt_n;
       {{
         const int64_t tn = t + 1 < T ? t + 1 : t;
@@ -617,75 +607,28 @@ __global__ __launch_bounds__(64) void k_run_pf(double* __restrict__ gx, double* 
       bool step = false;
       switch (kind) {{ {known} step = true; break; default: break; }}
       const bool pd = step && ({id0_guard});
-      stepped = stepped || step;
-      // ---- phase 1a / 2a: predict, per group on its own dt ----
-      if (c == 0 && step) {{
-        if (pd) scal_predict_r(sl + {lay.OFF_X}, dt, sl, norm_quats);
-        else scal_keep_r(sl + {lay.OFF_X}, sl, norm_quats);                 // predict(dt = 0) still renormalises
-      }}
-      rn::wave_lds_sync();
-      if (__any(pd)) {{
-        if (qdiag) {{
-          predict_rows_qd_pf({rows}, sP, {qd_args}, sl, {idx}, pd{_tl_arg(True)});
-        }} else {{
-          int qz = 0;
-          asm volatile("" : "+v"(qz));
-          predict_rows_pf({rows}, sP, gQ + qz, sl, {idx}, pd{_tl_arg(True)});
-        }}
-      }}
-      // ---- phase 1b / 2b: update, every kind present among the wavefront's filters ----
-      if (c == 0 && step) {{
+      stepped = stepped || step;""",
+    update=f"""      if (c == 0 && step) {{
         switch (kind) {{
 {scal_cases}
           default: break;
         }}
       }}
       rn::wave_lds_sync();
-{mat}
-      // ---- phase 3: lane 0 of each group injects the error state ----
-      if (c == 0 && live) {{
-        int fl = kind <= 0 ? 16 : 8;          // idle entry; a kind the model does not have: untouched either way
-        if (step) fl = scal_inject_r(sl, sl + {lay.OFF_X}, norm_quats) | (int)sl[{lay.OFF_FL}];
-        if (flags != nullptr) flags[t * n + base + g] = (uint8_t)fl;
-      }}
-      rn::wave_lds_sync();
-{z_out}
-      int lz = lane;
-      asm volatile("" : "+v"(lz));
-      if (tx != nullptr) {{
-        for (int i = lz; i < cnt * {D}; i += 64) tx[(t * n + base) * {D} + i] = s_sl[(i / {D}) * SLOT_R + {lay.OFF_X} + i % {D}];
-      }}
-      if (tP != nullptr) {{
-{img("")}
-        rn::wave_lds_sync();
-        rn::copy_l2g<FPWR * {EE}, {nt_trace}>(tP + (t * n + base) * {EE}, cnt * {EE}, s_P, lz);
-      }}
-      rn::wave_lds_sync();
-{z_commit}
-      rn::wave_lds_sync();
-    }}
-    // the image the filters came with, again: a filter that no entry stepped leaves as it came (x: its slot was never written)
-    int le = lane;
-    asm volatile("" : "+v"(le));
-    rn::copy_g2l<FPWR * {EE}>(gP + base * {EE}, cnt * {EE}, s_P, le);
-    rn::wave_lds_sync();
-{img(" && stepped")}
-    rn::wave_lds_sync();
-    rn::copy_l2g<FPWR * {EE}>(gP + base * {EE}, cnt * {EE}, s_P, le);
-    for (int i = le; i < cnt * {D}; i += 64) gx[base * {D} + i] = s_sl[(i / {D}) * SLOT_R + {lay.OFF_X} + i % {D}];
-    rn::wave_lds_sync();
-  }}
-}}
-"""
+{mat}""",
+    flags_rule=f"""        int fl = kind <= 0 ? 16 : 8;          // idle entry; a kind the model does not have: untouched either way
+        if (step) fl = scal_inject_r(sl, sl + {lay.OFF_X}, norm_quats) | (int)sl[{lay.OFF_FL}];""")
+
+
+def _launch(kname, more=""):
+  return f"""  const int64_t tiles = (n + FPWR - 1) / FPWR;
+  hipLaunchKernelGGL({kname}, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
+                     x, P, Q, kinds, dts, T, z, R, n, norm_quats, flags, trace_x, trace_P{more});"""
 
 
 def launch_run_pf():
-  return """  const int64_t tiles = (n + FPWR - 1) / FPWR;
-  hipLaunchKernelGGL(k_run_pf, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
-                     x, P, Q, kinds, dts, T, z, R, n, norm_quats, flags, trace_x, trace_P);"""
+  return _launch("k_run_pf")
 
 
 def launch_run():
-  return """  const int64_t tiles = (n + FPWR - 1) / FPWR;
-  hipLaunchKernelGGL(k_run, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
-                     x, P, Q, kinds, dts, T, z, R, n, norm_quats, flags, trace_x, trace_P, ea, augment);"""
+  return _launch("k_run", ", ea, augment")

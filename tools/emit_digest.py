@@ -14,7 +14,8 @@ KNOBS = ("small_zwait=0", "small_zwait=2", "small_split=0", "small_zwait=0,small
          "small_timeline=1,small_zwait=2,small_split=0", "small_waves=2", "run_block=-1")      # of the lane-per-filter step kernels
 FALLBACK_MODELS = {"force_wide": ("kinematic6", "attitude"), "no_run_blk": ("kinematic", "kinematic6"), "no_kinds": ("kinematic6", "kinematic9", "live"),
                    "no_model_defaults": ("live", "feature36"), "no_run2": ("live",), "no_tri": ("live",), "no_rts4": ("live",), "rts_one_wave": ("live",),
-                   "no_rts": ("live",), "no_run": ("rand40", "feature36")}      # models on which the fallback changes the text
+                   "no_rts": ("live",), "no_run": ("rand40", "feature36"),
+                   "no_run_pf": ("kinematic6", "kinematic9", "live", "rand17")}      # models on which the fallback changes the text
 GV_MODELS = ("gv_runtime", "gv_runtime10", "gv_extra")
 LANE_GROUP_KNOBS = {      # of the lane-group family: the branches of its step kernels, the fused runs and the smoother that no default model takes
   "live": ("wide_timeline=1", "wide_lean_q=0", "wide_inline=0", "wide_db=1,wide_ft=16", "wide_lean=0,wide_lb=0,wide_db=-1,wide_ft=0", "run2_prio=3",
