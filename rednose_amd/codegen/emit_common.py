@@ -191,20 +191,25 @@ def launch_predict(tiles):
   return _launch(tiles, "k_predict", "x, P, Q, dt_vec, dt, n, norm_quats, active")
 
 
-def _step_args(obs, do_predict):
+def _step_args(obs, do_predict, head=0):
+  """Arguments of a step kernel in its own order.  head=1 (the lane-per-filter family's tuning knob small_head): what the requests of a full tile need
+  comes first, within the 14 dwords that arrive preloaded in SGPRs, r_per_filter and norm_quats packed into one int (bits 0 and 1)."""
+  if head:
+    return (f"x, P, z, n, {'Q' if do_predict else 'nullptr'}, R, (r_per_filter != 0 ? 1 : 0) | (norm_quats != 0 ? 2 : 0), {obs}, "
+            f"{'dt_vec, dt' if do_predict else 'nullptr, 0.0'}, flags, active")
   return f"x, P, z, R, r_per_filter, {obs}, {'Q, dt_vec, dt' if do_predict else 'nullptr, nullptr, 0.0'}, n, norm_quats, flags, active"
 
 
-def launch_step(tiles, kind, do_predict):
-  return _launch(tiles, f"k_step_{kind}<{'true' if do_predict else 'false'}>", _step_args("ea", do_predict))
+def launch_step(tiles, kind, do_predict, head=0):
+  return _launch(tiles, f"k_step_{kind}<{'true' if do_predict else 'false'}>", _step_args("ea", do_predict, head))
 
 
-def launch_step_ckpt(tiles, kind):
-  return _launch(tiles, f"k_stepc_{kind}<true>", _step_args("ea", True) + ", ckpt_x, ckpt_P, ckpt_z")
+def launch_step_ckpt(tiles, kind, head=0):
+  return _launch(tiles, f"k_stepc_{kind}<true>", _step_args("ea", True, head) + ", ckpt_x, ckpt_P, ckpt_z")
 
 
-def launch_kinds(tiles, do_predict):
-  return _launch(tiles, f"k_kinds<{'true' if do_predict else 'false'}>", _step_args("kinds", do_predict))
+def launch_kinds(tiles, do_predict, head=0):
+  return _launch(tiles, f"k_kinds<{'true' if do_predict else 'false'}>", _step_args("kinds", do_predict, head))
 
 
 def launch_maha(tiles, kind, ea=True):

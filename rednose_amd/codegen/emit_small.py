@@ -25,7 +25,8 @@ Where things are: predict_regs / update_regs / maha_regs print the algebra on re
 then step_kernel() for k_step_{kind}, k_stepc_{kind} (+ checkpoint) and -- through kinds_kernel() -- k_kinds (a kind per filter); it is made of
 named pieces (LDS images, TILE_LOOP, the tile requests with z last and a counted wait or all behind one wait, predict + pins, the split and the
 unsplit write-back, the non-finite test, the timeline stamps) of which k_predict, k_maha_{kind} and k_run take those that apply.  kind_cases()
-is the per-kind `switch` of k_kinds, k_run, k_run_blk and k_run_blk_tr.  The launch text of the step-granular kernels is emit_common's, bound to
+is the per-kind `switch` of k_kinds, k_run, k_run_blk and k_run_blk_tr.  _step_head() / predict_kernel() are the frame of the step kernels and of
+k_predict under the tuning knob small_head (default): the same pieces with the first tile's requests at the very top and the tile loop rotated.  The launch text of the step-granular kernels is emit_common's, bound to
 this family's TILES; launch_run is this family's own.
 """
 import functools
@@ -360,7 +361,7 @@ def kind_cases(spec, suffix, z, R, R_shared=None, extra="", ea_lane=None, ind=8)
 def kernels(spec):
   """Device functions + __global__ kernels of family S for every kind."""
   tune = tuning.current()
-  waves, split = tune.small_waves, bool(tune.small_split)
+  waves, split, head = tune.small_waves, bool(tune.small_split), bool(tune.small_head)
   kattr = f" __attribute__((amdgpu_waves_per_eu({waves}, {waves})))" if waves else ""
   D, E = spec.dim_x, spec.dim_err
   EE = E * E
@@ -393,12 +394,31 @@ template <int EPF> inline void wait_but_tile(int) {}
 inline void lane_dt_request(const double* g_lane, double* lds, int lane) { lds[lane] = *g_lane; }
 inline double lane_dt(const double* lds, int lane) { return lds[lane]; }
 #endif
+""" if not head else """
+// What the step kernels use of the runtime beyond the tile copies: the counted waits, the per-filter dt and the shared Q as LDS-DMA transfers
+// (templates/ekf_hip_rt.h), and the point the instruction scheduler moves nothing across.  A host build of this text (the kernels run lane by
+// lane as threads, every copy synchronous) has nothing to wait for and nothing to hold.
+#ifdef __HIP__
+template <int EPF> __device__ __forceinline__ void wait_but_tile(int cnt) { rn::async_wait_but_tile<EPF>(cnt); }
+template <int N> __device__ __forceinline__ void wait_but_loads(int cnt) { rn::async_wait_but_loads<N>(cnt); }
+__device__ __forceinline__ void lane_dt_request(const double* g_lane, double* lds, int lane) { (void)lane; rn::lane_double_g2l_async(g_lane, lds); }
+__device__ __forceinline__ double lane_dt(const double* lds, int lane) { return rn::lane_double_from_lds(lds, lane); }
+template <int ND> __device__ __forceinline__ void shared_request(const double* g, double* lds, int lane) { rn::doubles_g2l_async<ND>(g, lds, lane); }
+__device__ __forceinline__ void hold_order() { __builtin_amdgcn_sched_barrier(0); }
+#else
+template <int EPF> inline void wait_but_tile(int) {}
+template <int N> inline void wait_but_loads(int) {}
+inline void lane_dt_request(const double* g_lane, double* lds, int lane) { lds[lane] = *g_lane; }
+inline double lane_dt(const double* lds, int lane) { return lds[lane]; }
+template <int ND> inline void shared_request(const double* g, double* lds, int lane) { for (int i = lane; i < ND; i += 64) lds[i] = g[i]; }
+inline void hold_order() {}
+#endif
 """)
   norm = norm_text(spec)
   if tune.small_timeline:
     out.append("__device__ unsigned long long g_tl[256 * 8 * 2];      // debug timeline (tuning knob small_timeline)")
 
-  out.append(f"""
+  out.append(predict_kernel(spec, norm) if head else f"""
 // ---- predict only: one launch propagates n filters by dt -------------------------------------------
 __global__ __launch_bounds__(64) void k_predict(double* __restrict__ gx, double* __restrict__ gP,
     const double* __restrict__ gQ, const double* __restrict__ gdt, const double dt_scalar, const int64_t n,
@@ -434,11 +454,11 @@ __global__ __launch_bounds__(64) void k_predict(double* __restrict__ gx, double*
 """)
   # k_stepc_{kind}: the same kernel writing a CHECKPOINT on its way -- the observations as they came (cz) and the filtered pair (cx, cP): what the
   # orchestrators' rewind rings keep of every call (ekf_sym.cc:142-156, 191).  A kernel of its own, so that k_step_{kind} stays as it is.
-  knobs = dict(kattr=kattr, split=split, zwait=tune.small_zwait, tline=bool(tune.small_timeline))
+  knobs = dict(kattr=kattr, split=split, zwait=tune.small_zwait, tline=bool(tune.small_timeline), head=head and tune.small_zwait == 1)
   out += [step_kernel(spec, norm, k, ckpt, **knobs) for k in spec.kinds for ckpt in (False, True)]
   from rednose_amd.codegen import emit      # (emit imports this module: see its docstring)
   if emit.step_kinds(spec):
-    out.append(kinds_kernel(spec, norm, kattr, split))
+    out.append(kinds_kernel(spec, norm, kattr, split, head))
   if run_block(spec) > 0:          # blocked fused runs: k_run_blk (no trace) and k_run_blk_tr (filtered trace)
     out.append(run_kernel_blk(spec, norm))
     out.append(run_kernel_blk(spec, norm, trace=True))
@@ -450,7 +470,7 @@ __global__ __launch_bounds__(64) void k_predict(double* __restrict__ gx, double*
   return "\n".join(out)
 
 
-def kinds_kernel(spec, norm, kattr="", split=False):
+def kinds_kernel(spec, norm, kattr="", split=False, head=False):
   """k_kinds: the step kernel in which every filter brings its own observation kind (kinds[i]).  The tile is loaded once -- z rows and per-filter
   R at the strides of the fused run, zmax and zmax^2 --, predicted once, and a per-lane switch over the model's kinds calls update_{k}_regs:
   a wavefront pays the sum of the kinds present among its 64 filters in arithmetic, and one trip through HBM.  A filter that is masked out, or
@@ -458,13 +478,15 @@ def kinds_kernel(spec, norm, kattr="", split=False):
   The load order is that of small_zwait == 1 (z last, counted wait) whatever the knob says -- the knob's alternatives exist for the per-kind
   kernels' A/B runs only --, s_R is allocated whether or not R comes per filter, and a shared R is read from the table inside the switch (one
   load per kind present in the wavefront).  This family's kernel is covered by tests; its time has not been measured."""
-  return step_kernel(spec, norm, None, kattr=kattr, split=split)
+  return step_kernel(spec, norm, None, kattr=kattr, split=split, head=head)
 
 
-def step_kernel(spec, norm, k, ckpt=False, kattr="", split=False, zwait=1, tline=False):
+def step_kernel(spec, norm, k, ckpt=False, kattr="", split=False, zwait=1, tline=False, head=False):
   """The step kernels, [predict +] update with the state round-tripping HBM once per launch: k_step_{kind} of kind k, k_stepc_{kind} (ckpt: the same
   writing the call's checkpoint), and with k = None k_kinds (see kinds_kernel; x, z and P leave together there, after the switch).
-  `zwait`, `split`, `tline`: the tuning knobs small_zwait, small_split, small_timeline."""
+  `zwait`, `split`, `tline`, `head`: the tuning knobs small_zwait, small_split, small_timeline, small_head (head: see _step_head, which puts the
+  pieces made here into its own frame; it takes the request order of zwait == 1)."""
+  assert not head or zwait == 1
   mixed = k is None
   D, E = spec.dim_x, spec.dim_err
   EE = E * E
@@ -483,11 +505,17 @@ def step_kernel(spec, norm, k, ckpt=False, kattr="", split=False, zwait=1, tline
   tl_decl = f"""
     const bool tl_on = tile == blockIdx.x && blockIdx.x < 256;
     unsigned long long tl_c[7] = {{0, 0, 0, 0, 0, 0, 0}}, tl_w[7] = {{0, 0, 0, 0, 0, 0, 0}};{TL(0)}""" if tline else ""
+  if tline and head:      # the entry stamp stands in front of the first tile's requests, outside the rotated loop; only the first tile is stamped
+    tl_decl = f"""
+  bool tl_on = blockIdx.x < 256;
+  unsigned long long tl_c[7] = {{0, 0, 0, 0, 0, 0, 0}}, tl_w[7] = {{0, 0, 0, 0, 0, 0, 0}};{TL(0).replace(chr(10) + "    ", chr(10) + "  ")}"""
   tl_out = f"""{TL(6)}
     if (tl_on && lane == 0) {{
 #pragma unroll
       for (int i = 0; i < 7; i++) {{ g_tl[(blockIdx.x * 8 + i) * 2] = tl_c[i]; g_tl[(blockIdx.x * 8 + i) * 2 + 1] = tl_w[i]; }}
     }}""" if tline else ""
+  if tline and head:
+    tl_out += "\n    tl_on = false;"
 
   # ---- the tile's requests, and what reads them out of LDS
   tile_x, tile_P, tile_z = _tile_in(D, "gx", "s_x"), _tile_in(EE, "gP", "s_P"), _tile_in(Z, "gz", "s_z")
@@ -517,12 +545,13 @@ def step_kernel(spec, norm, k, ckpt=False, kattr="", split=False, zwait=1, tline
     # update, after 42 LDS reads and the whole predict; in a stream they are also the slowest tile (a buffer nothing has touched since it was
     # written: HBM, while x and P were written by the previous launch and sit in the L2 / Infinity Cache)
     pin_note = "" if mixed else "\n    // (the predict's arithmetic ends here: without the pins hipcc sinks it below the wait, into the update's)"
-    load = f"""{tile_x}
+    requests = f"""{tile_x}
     {tile_P}
     {tile_R}
     {tile_dt}
     {tile_z}{TL(1)}{act}
-    wait_but_tile<{Z}>(cnt);
+    wait_but_tile<{Z}>(cnt);"""
+    landed = f"""
     rn::wave_lds_sync();{TL(2)}
     {regs}
     {read_dt}
@@ -533,6 +562,7 @@ def step_kernel(spec, norm, k, ckpt=False, kattr="", split=False, zwait=1, tline
     rn::async_wait();
     rn::wave_lds_sync();{TL(3)}{cz_store}
     {read_zR}"""
+    load = requests + landed
   else:
     # all tiles, one wait; 0: the observations first (they are the slowest tile, see above), 2: between x and P
     order = [tile_z, tile_R, tile_x, tile_P] if zwait == 0 else [tile_x, tile_R, tile_z, tile_P]
@@ -614,6 +644,9 @@ def step_kernel(spec, norm, k, ckpt=False, kattr="", split=False, zwait=1, tline
 #pragma unroll
       for (int i = 0; i < {ZZ}; i++) R[i] = gR[i];
     }}"""
+  flags_out = f"if (flags != nullptr && lane < cnt) flags[base + lane] = (uint8_t)(on ? (fl | nf) : {'(live ? 8 : 16)' if mixed else '16'});{tl_out}"
+  if head:
+    return _step_head(locals())
   return f"""
 {title}
 template <bool DO_PREDICT>
@@ -630,15 +663,165 @@ __global__ __launch_bounds__(64){kattr} void {kn}(double* __restrict__ gx, doubl
 {TILE_LOOP}{tl_decl}{shared_R}
     {load}
     {update}
-    if (flags != nullptr && lane < cnt) flags[base + lane] = (uint8_t)(on ? (fl | nf) : {'(live ? 8 : 16)' if mixed else '16'});{tl_out}
+    {flags_out}
     rn::wave_lds_sync();
   }}
 }}
 """
 
 
-launch_predict, launch_step, launch_step_ckpt, launch_kinds = (functools.partial(f, TILES) for f in (
-  emit_common.launch_predict, emit_common.launch_step, emit_common.launch_step_ckpt, emit_common.launch_kinds))
+NEXT_TILE = """    tile += gridDim.x;
+    if (tile >= tiles) break;
+    base = tile << 6;
+    cnt = (n - base) < 64 ? (int)(n - base) : 64;"""
+FIRST_TILE = """  const int64_t tiles = (n + 63) >> 6;
+  int64_t tile = blockIdx.x;
+  if (tile >= tiles) return;
+  int64_t base = tile << 6;
+  int cnt = (n - base) < 64 ? (int)(n - base) : 64;"""
+
+
+def _step_head(p):
+  """The step kernels with nothing in front of the first tile's requests (tuning knob small_head = 1); p: the pieces step_kernel made.
+
+  * Signature: gx, gP, gz, n, gQ, gR and `opts` (bit 0: r_per_filter, bit 1: norm_quats) are the first 13 dwords of the kernel arguments, which arrive
+    preloaded in SGPRs (rednose_amd/build.py: -amdgpu-kernarg-preload-count): the requests of x, P, a per-filter R and Q wait for no s_load.  The
+    other arguments are loaded at the top as before; their wait stands behind those requests, in front of the per-filter dt, the mask, the kinds.
+  * The tile loop is rotated: the first tile is requested outside it, its body is wait, compute, store, request the next tile.  hipcc cannot
+    hoist the loop's invariants (the addresses of the write-back, the lane masks of the ragged copies) in front of requests that stand outside
+    the loop, and hold_order() keeps its scheduler from moving anything across the end of the requests.
+  * Q comes by LDS-DMA with the tile, into s_Q, once (it does not change from tile to tile).  A shared R is an ordinary load behind the first
+    requests, once as well.
+  * One list of requests, in issue order, makes both the text and the operand of the counted wait: vmcnt retires in issue order, so what may stay
+    in flight under the predict is what stands behind the last request the predict reads -- the observation tile.  The mask and the kinds are
+    ordinary loads in front of it.  (hipcc may move an ordinary load; whichever way it moves, no fewer transfers than counted are issued behind
+    the predict's last operand, so the wait can only be stronger than written, never weaker.)  A ragged tile goes through registers and waits
+    for everything, Q included."""
+  D, EE, Z, ZZ, mixed = p["D"], p["EE"], p["Z"], p["ZZ"], p["mixed"]
+  TL = p["TL"]
+
+  def loads(epf):      # global_load_lds instructions of tile_g2l_async<epf> on a full tile (rn::tile_async_loads)
+    return (32 * epf + 63) // 64
+  mask = "if (active != nullptr) act = active[base + (lane < cnt ? lane : cnt - 1)];"
+  kinds = "kind = gkinds[base + (lane < cnt ? lane : cnt - 1)];"
+  # (text, transfers it issues on a full tile, first tile only, read by the predict or before it)
+  shared_R = "" if mixed else f"""// a shared R: ordinary loads, once (it does not change from tile to tile), first used by the update
+  double R[{ZZ}];
+  if (!r_per_filter) {{
+#pragma unroll
+    for (int i = 0; i < {ZZ}; i++) R[i] = gR[i];
+  }}"""
+  reqs = [(p["tile_x"], loads(D), False, True), (p["tile_P"], loads(EE), False, True), (p["tile_R"], loads(ZZ), False, True),
+          (shared_R, 0, True, True),
+          (f"if (DO_PREDICT) shared_request<{EE}>(gQ, s_Q, lane);", (2 * EE + 63) // 64, True, True),
+          ("hold_order();      // the arguments beyond the preloaded ones are first used below: their wait stands behind the requests above", 0, False, True),
+          (p["tile_dt"], 2, False, True), (mask, 0, False, True)] + ([(kinds, 0, False, True)] if mixed else []) + [
+          (p["tile_z"], loads(Z), False, False), ("hold_order();", 0, False, False)]
+  last_needed = max(i for i, r in enumerate(reqs) if r[3])
+  in_flight = sum(r[1] for r in reqs[last_needed + 1:])      # the operand of the counted wait
+
+  def requests(first, pad):
+    return ("\n" + pad).join(r[0] for r in reqs if r[0] and (first or not r[2])) + TL(1)
+  mask_note = ("// a filter that is masked out, or whose kind the model does not have, is not written back (flags 16 / 8)" if mixed else
+               "// masked-out filters (active[i] == 0) pass through untouched: x, P and z leave as they came, flag bit 4 is set")
+  obs = "const int32_t* __restrict__ gkinds" if mixed else "const double* __restrict__ gea"
+  kn, cargs = p["kn"], p["cargs"]
+  # host builds of this text (tests/test_emit_host*.py) call the kernels in the argument order of the C ABI
+  cnames = ", cx, cP, cz" if cargs else ""
+  host_order = f"""#ifndef __HIP__
+template <bool DO_PREDICT> void {kn}(double* gx, double* gP, double* gz, const int64_t n, const double* gQ, const double* gR, const int opts, {obs.replace("__restrict__ ", "")}, const double* gdt, const double dt_scalar, uint8_t* flags, const uint8_t* active{cargs.replace("__restrict__ ", "")});
+template <bool DO_PREDICT> inline void {kn}(double* gx, double* gP, double* gz, const double* gR, const int r_per_filter, {obs.replace("__restrict__ ", "")}, const double* gQ, const double* gdt, const double dt_scalar, const int64_t n, const int norm_quats, uint8_t* flags, const uint8_t* active{cargs.replace("__restrict__ ", "")}) {{ {kn}<DO_PREDICT>(gx, gP, gz, n, gQ, gR, (r_per_filter != 0 ? 1 : 0) | (norm_quats != 0 ? 2 : 0), {'gkinds' if mixed else 'gea'}, gdt, dt_scalar, flags, active{cnames}); }}
+#endif"""
+  return f"""
+{p["title"]}
+{host_order}
+template <bool DO_PREDICT>
+__global__ __launch_bounds__(64){p["kattr"]} void {kn}(double* __restrict__ gx, double* __restrict__ gP, double* __restrict__ gz, const int64_t n,
+    const double* __restrict__ gQ, const double* __restrict__ gR, const int opts, {obs},
+    const double* __restrict__ gdt, const double dt_scalar, uint8_t* __restrict__ flags, const uint8_t* __restrict__ active{cargs}) {{
+{_lds(x=D, P=EE, z=Z, R=ZZ)}
+{_lds(True, Q=EE, dt=64)}
+  const int lane = threadIdx.x;
+  const int r_per_filter = opts & 1, norm_quats = opts & 2;
+{FIRST_TILE}{p["tl_decl"] if p["tline"] else ""}
+  uint8_t act = 1;{f"{chr(10)}  int kind = 0;" if mixed else ""}
+  {requests(True, "  ")}
+  for (;;) {{
+    {mask_note}
+    wait_but_loads<{in_flight}>(cnt);{p["landed"]}
+    {p["update"]}
+    {p["flags_out"]}
+    rn::wave_lds_sync();
+{NEXT_TILE}
+    {requests(False, "    ")}
+  }}
+}}
+"""
+
+
+def predict_kernel(spec, norm):
+  """k_predict with the prologue of small_head = 1 (see _step_head): its arguments but the mask are all within the preloaded ones as they stand."""
+  D, E = spec.dim_x, spec.dim_err
+  EE = E * E
+  dt = "dt = (gdt != nullptr && lane < cnt) ? gdt[base + lane] : dt_scalar;"
+  return f"""
+// ---- predict only: one launch propagates n filters by dt -------------------------------------------
+__global__ __launch_bounds__(64) void k_predict(double* __restrict__ gx, double* __restrict__ gP,
+    const double* __restrict__ gQ, const double* __restrict__ gdt, const double dt_scalar, const int64_t n,
+    const int norm_quats, const uint8_t* __restrict__ active) {{
+{_lds(x=D, P=EE)}
+{_lds(True, Q=EE)}
+  const int lane = threadIdx.x;
+{FIRST_TILE}
+  {_tile_in(D, "gx", "s_x")}
+  {_tile_in(EE, "gP", "s_P")}
+  shared_request<{EE}>(gQ, s_Q, lane);       // Q as LDS broadcast operands (36 SGPR pairs spilled otherwise), requested with the first tile
+  double {dt}
+  hold_order();
+  for (;;) {{
+    rn::async_wait();
+    rn::wave_lds_sync();
+    double x[{D}], P[{EE}];
+    rn::lds_to_regs<{D}>(s_x, lane, x);
+    rn::lds_to_regs<{EE}>(s_P, lane, P);
+    predict_regs(x, P, s_Q, dt);
+    {norm}
+    rn::wave_lds_sync();
+    // a masked-out filter (active[i] == 0: no observation for it in this call) keeps the record it came with: its lane
+    // does not overwrite the LDS image, so the coalesced write-back returns the loaded bytes
+    if (active == nullptr || (lane < cnt && active[base + lane] != 0)) {{
+      rn::regs_to_lds<{D}>(s_x, lane, x);
+      rn::regs_to_lds<{EE}>(s_P, lane, P);
+    }}
+    rn::wave_lds_sync();
+    {_tile_out(D, "gx", "s_x")}
+    {_tile_out(EE, "gP", "s_P")}
+    rn::wave_lds_sync();
+{NEXT_TILE}
+    {_tile_in(D, "gx", "s_x")}
+    {_tile_in(EE, "gP", "s_P")}
+    {dt}
+    hold_order();
+  }}
+}}
+"""
+
+
+def launch_step(kind, do_predict):
+  t = tuning.current()
+  return emit_common.launch_step(TILES, kind, do_predict, head=bool(t.small_head) and t.small_zwait == 1)
+
+
+def launch_step_ckpt(kind):
+  t = tuning.current()
+  return emit_common.launch_step_ckpt(TILES, kind, head=bool(t.small_head) and t.small_zwait == 1)
+
+
+def launch_kinds(do_predict):
+  return emit_common.launch_kinds(TILES, do_predict, head=bool(tuning.current().small_head))
+
+
+launch_predict = functools.partial(emit_common.launch_predict, TILES)
 launch_maha = functools.partial(emit_common.launch_maha, TILES, ea=False)      # this family's k_maha_{kind} has no extra-argument parameter
 
 

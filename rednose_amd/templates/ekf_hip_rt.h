@@ -405,6 +405,37 @@ __device__ __forceinline__ void async_wait_but_tile(int cnt) {
 #endif
 }
 
+// The same with the count given: everything but the LAST N transfers of the full-tile path has landed (N: what the caller requested behind the
+// last thing it is about to read).  Ragged tiles, and the padded image, went through registers: everything is waited for.
+template <int N>
+__device__ __forceinline__ void async_wait_but_loads(int cnt) {
+#if RN_LDS_PAD
+  (void)cnt;
+  async_wait();
+#else
+  if (cnt == WAVE) async_wait_but<N>(); else async_wait();
+#endif
+}
+
+// ND contiguous doubles shared by the wavefront (a model's Q), HBM -> LDS without a register in between and without a wait of their own: they
+// ride with the tile requests and land under the caller's counted wait.  4-byte transfers, lane l taking words l, l + 64, ...: any 8-byte
+// aligned source, any ND (a lane past the end issues nothing; the LDS address of a lane is base + lane * 4 whatever the others do).
+template <int ND>
+__device__ __forceinline__ void doubles_g2l_async(const double* __restrict__ g, double* lds, int lane) {
+  constexpr int NW = 2 * ND;
+  const char* p = reinterpret_cast<const char*>(g);
+#pragma unroll
+  for (int i = 0; i < (NW + WAVE - 1) / WAVE; i++) {
+    const int idx = lane + i * WAVE;
+    if ((NW % WAVE == 0) || idx < NW) {
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p + 4 * idx), lds_offset_ptr(lds + i * (WAVE / 2)), 4, 0, 0);
+    }
+  }
+}
+// transfers doubles_g2l_async<ND> issues
+template <int ND>
+__device__ __forceinline__ constexpr int doubles_async_loads() { return (2 * ND + WAVE - 1) / WAVE; }
+
 // One double per lane, HBM -> LDS without a register in between (an ordinary load would make hipcc wait for vmcnt(0) at its first use, i.e.
 // for every tile in flight): two 4-byte transfers, low words to the 64 words at `lds`, high words to the 64 behind them.  Any 8-byte aligned
 // source.  lane_double_from_lds() after async_wait / async_wait_but + wave_lds_sync.

@@ -2,7 +2,10 @@
 """sha256 of `{name}.h` / `{name}.hip` as emitted (nothing compiled: no GPU, no hipcc) over models x fallbacks x tuning knobs, a line each.
 A change to the emitters that must leave every generated text as it is: run it with --tree on the parent checkout and on the branch, compare.
 
-  python tools/emit_digest.py OUT.txt [--tree OTHER_CHECKOUT] [--jobs N]"""
+  python tools/emit_digest.py OUT.txt [--tree OTHER_CHECKOUT] [--jobs N] [--with KNOB=V,..]
+
+--with appends knob settings to every configuration's RN_TUNE and leaves the labels as they are: a knob whose value V is meant to reproduce a parent
+that does not know the knob (small_head=0) is checked by comparing that file with the parent's own, line by line."""
 import argparse
 import hashlib
 import os
@@ -12,6 +15,7 @@ from concurrent.futures import ProcessPoolExecutor
 
 KNOBS = ("small_zwait=0", "small_zwait=2", "small_split=0", "small_zwait=0,small_split=0", "small_timeline=1", "small_timeline=1,small_zwait=0",
          "small_timeline=1,small_zwait=2,small_split=0", "small_waves=2", "run_block=-1")      # of the lane-per-filter step kernels
+HEAD_KNOBS = ("small_head=0", "small_head=0,small_timeline=1", "small_head=0,small_split=0")      # the prologue before small_head (appended at the end, see configurations)
 FALLBACK_MODELS = {"force_wide": ("kinematic6", "attitude"), "no_run_blk": ("kinematic", "kinematic6"), "no_kinds": ("kinematic6", "kinematic9", "live"),
                    "no_model_defaults": ("live", "feature36"), "no_run2": ("live",), "no_tri": ("live",), "no_rts4": ("live",), "rts_one_wave": ("live",),
                    "no_rts": ("live",), "no_run": ("rand40", "feature36"),
@@ -34,7 +38,8 @@ def configurations():
   cfg += [(n, "", fb) for fb in emit.FALLBACKS for n in FALLBACK_MODELS[fb]]
   cfg += [(n, kn, None) for n in ("kinematic6", "attitude") for kn in KNOBS] + [("kinematic9", "wide_timeline=1", None)]
   cfg += [(n, "", None) for n in GV_MODELS]      # appended to, never reordered: earlier digest files stay a prefix of later ones
-  return cfg + [(n, kn, None) for n, knobs in LANE_GROUP_KNOBS.items() for kn in knobs]
+  cfg += [(n, kn, None) for n, knobs in LANE_GROUP_KNOBS.items() for kn in knobs]
+  return cfg + [(n, kn, None) for n in ("kinematic6", "attitude") for kn in HEAD_KNOBS]
 
 
 def gv_spec(name):
@@ -76,7 +81,7 @@ def example_spec(name):
 def digest(cfg):
   from rednose_amd.codegen import emit
   name, tune, fb = cfg
-  os.environ["RN_TUNE"] = tune
+  os.environ["RN_TUNE"] = ",".join(t for t in (tune, os.environ.get("RN_DIGEST_WITH", "")) if t)
   hdr, src = emit.emit(gv_spec(name) if name in GV_MODELS else example_spec(name), (fb,) if fb else ())
   label = name + (f" RN_TUNE={tune}" if tune else "") + (f" fallback={fb}" if fb else "")
   return f"{label}: h {hashlib.sha256(hdr.encode()).hexdigest()} hip {hashlib.sha256(src.encode()).hexdigest()}"
@@ -87,7 +92,9 @@ if __name__ == "__main__":
   ap.add_argument("out")
   ap.add_argument("--tree", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."), help="checkout to take rednose_amd and examples from")
   ap.add_argument("--jobs", type=int, default=4)
+  ap.add_argument("--with", dest="extra", default="", help="knob settings appended to every configuration's RN_TUNE (labels unchanged)")
   args = ap.parse_args()
+  os.environ["RN_DIGEST_WITH"] = args.extra
   tree = os.path.abspath(args.tree)
   sys.path.insert(0, tree)
   with ProcessPoolExecutor(args.jobs, initializer=sys.path.insert, initargs=(0, tree)) as ex:
