@@ -315,6 +315,26 @@ extern "C" {
                                 int64_t T, double *z, const double *R, int64_t n, int norm_quats, uint8_t *flags, \
                                 double *trace_x, double *trace_P, void *stream);
 
+/* THE SAME RUN WITH A NOISE MATRIX PER LOG ENTRY.  A recorded log carries the noise of each observation (a GNSS fix with the receiver's
+ * reported variance, an odometry frame with its own standard deviation); batch_run_pf knows one R per kind for the whole run.  Here
+ * every entry (t, i) brings its own R, as every predict_and_update_batch(t, kind, z, R) call of the reference does.
+ *   {name}_has_batch_run_pf_r() == 1: the library has the kernel.  0: a library without batch_run_pf, or one whose kernel did not fit the
+ *   register file -- batch_run_pf_r then returns status 4 and nothing is launched (walk the schedule with batch_predict_update_kinds and
+ *   r_per_filter != 0, one step's rows at a time).
+ * Every argument is batch_run_pf's, and so are the status codes, the argument checks (NULL -> 2, misaligned -> 3, T == 0 or n == 0 a no-op
+ * that returns 0, no device -> 1), the alignment rules, the flag rules 16 / 8, the dense trace, (P + P^T) / 2 at entry, and "a filter that
+ * no entry stepped is not written back".  What differs is R:
+ *   R is a DEVICE array (T, n, zmax * zmax), 16-byte aligned.  The leading Z * Z doubles of row (t, i) are the row-major R of entry (t, i),
+ *   Z being the Z of kinds[t, i]: R + t * n * zmax * zmax is exactly the `r_per_filter != 0` buffer of batch_predict_update_kinds for step t.
+ *   The rest of a row is never used, and neither are the rows of idle entries (kinds[t, i] <= 0) and of entries with an unknown kind
+ *   (flag 8): such doubles may hold anything, NaN included, and nothing of them reaches x, P, y, the flags or the trace.  The R of an entry
+ *   is symmetric positive definite, like the rows of the table. */
+#define RN_DECLARE_BATCH_RUN_PF_R(name)                                                                          \
+  int RN_FN(name, has_batch_run_pf_r)(void);                                                                     \
+  int RN_FN(name, batch_run_pf_r)(double *x, double *P, const double *Q, const int32_t *kinds, const double *dts, \
+                                  int64_t T, double *z, const double *R, int64_t n, int norm_quats,               \
+                                  uint8_t *flags, double *trace_x, double *trace_P, void *stream);
+
 /* Per-filter timelines, THE LATE OBSERVATION ON THE DEVICE: the rewind of every filter batch_timeline_plan found late, each in its own ring
  * (EKF_sym.rewind and the too-old test in front of it, the reference's ekf_sym.py:418-438, 464-471), and the gather of the
  * overtaken entries, one replay position of all rewound filters at a time, into the buffers batch_predict_update_kinds and

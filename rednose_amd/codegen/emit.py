@@ -48,7 +48,10 @@ SMALL_MAX_E = 7    # lane-per-filter register budget: x, P and the update's temp
 #                      it ({name}_has_step_kinds() == 0, its entry points return ERR_UNSUPPORTED; one `_masked` launch per kind serves such a call)
 #   no_run_pf          the fused run with a schedule per filter (k_run_pf / k_run_pf_tr) touches scratch memory or spills -> library without it
 #                      ({name}_has_batch_run_pf() == 0, batch_run_pf returns ERR_UNSUPPORTED; BatchedEKF.run_logs walks such logs step by step)
-FALLBACKS = ("force_wide", "no_model_defaults", "no_rts4", "rts_one_wave", "no_rts", "no_run2", "no_run", "no_run_blk", "no_tri", "no_kinds", "no_run_pf")
+#   no_run_pf_r        the fused run with a schedule per filter and a noise matrix per entry (k_run_rpf / k_run_rpf_tr) touches scratch memory or spills ->
+#                      library without it ({name}_has_batch_run_pf_r() == 0, batch_run_pf_r returns ERR_UNSUPPORTED); k_run_pf and everything else stay
+FALLBACKS = ("force_wide", "no_model_defaults", "no_rts4", "rts_one_wave", "no_rts", "no_run2", "no_run", "no_run_blk", "no_tri", "no_kinds", "no_run_pf",
+             "no_run_pf_r")
 KINDS_MAX = 16      # kinds of a model with a mixed-kind step: the Z table rn::k_timeline_push takes by value
 _active = frozenset()      # fallbacks of the emit() call in progress
 
@@ -79,6 +82,13 @@ def run_pf(spec, fallbacks=None):
   if "no_run_pf" in fb or "no_run" in fb or spec.N > 0 or spec.dim_err > 64:
     return False
   return all(k.ea_sym is None and k.He_sym is None and k.kind > 0 for k in spec.kinds)
+
+
+def run_pf_r(spec, fallbacks=None):
+  """Does this library get the fused run with a schedule per filter AND a noise matrix per entry (k_run_rpf: emit_small.run_rpf_kernel,
+  emit_wide3.run_rpf_kernel)?  At most where run_pf() is."""
+  fb = _active if fallbacks is None else fallbacks
+  return "no_run_pf_r" not in fb and run_pf(spec, fb)
 
 
 def _align2(n):
@@ -147,8 +157,9 @@ class _Abi:
 
 
 def _aligned16(ptrs):
-  """The 16-byte condition on device pointers (R only where it is per filter: a shared R is read with scalar loads)."""
-  return " && ".join("(!r_per_filter || rn::aligned16(R))" if p == "R" else f"rn::aligned16({p})" for p in ptrs)
+  """The 16-byte condition on device pointers (R only where it is per filter: a shared R is read with scalar loads; "R per entry": the
+  entry point has no such switch, its R is always per entry)."""
+  return " && ".join("(!r_per_filter || rn::aligned16(R))" if p == "R" else f"rn::aligned16({p.split()[0]})" for p in ptrs)
 
 
 def _batched(require, aligned, launch, require2=None, empty="n == 0", decl="", hip_check=True):
@@ -172,9 +183,10 @@ RTS_PARAMS = ("const double *xf, const double *Pf, const double *ts, int64_t T, 
               "const double *x_last, const double *P_last, void *stream")
 
 
-def _run_body(launch, hip_check=True):
-  return _batched("n >= 0 && T >= 0 && x && P && Q && kinds && dts && z && R", ["x", "P", "z", "trace_x", "trace_P"], launch, empty="n == 0 || T == 0",
-                  hip_check=hip_check)
+def _run_body(launch, hip_check=True, r_per_entry=False):
+  """r_per_entry: R is (T, n, zmax^2) (batch_run_pf_r), read by the lanes and 16-byte aligned like x, P and z."""
+  return _batched("n >= 0 && T >= 0 && x && P && Q && kinds && dts && z && R", ["x", "P", "z", "trace_x", "trace_P"] + (["R per entry"] if r_per_entry else []),
+                  launch, empty="n == 0 || T == 0", hip_check=hip_check)
 
 
 def _unsupported(why, unused=""):
@@ -190,11 +202,12 @@ def _select(spec):
               (use_rts4; emit_rts4: 8 .. 22 error states) or rn::k_rts_group (MSCKF models -- their main block is smoothed, ekf_sym.py:675-686 --,
               larger models, and the fallback of k_rts4)
     use_tri   packed-triangle trace: both structures or neither (batch_run_tri writes what batch_rts_tri reads)
-    has_kinds the mixed-kind step kernel k_kinds;  has_run_pf: the fused run with a schedule per filter (k_run_pf)"""
+    has_kinds the mixed-kind step kernel k_kinds;  has_run_pf: the fused run with a schedule per filter (k_run_pf);  has_run_pf_r: the same with a
+              noise matrix per entry (k_run_rpf)"""
   if spec.dim_err > 64:
     raise NotImplementedError(f"{spec.dim_err} error states: the lane-group kernels hold one row of P per lane of a wavefront (<= 64)")
   tune = tuning.current()
-  s = types.SimpleNamespace(fam=family(spec), has_run="no_run" not in _active, has_kinds=step_kinds(spec), has_run_pf=run_pf(spec))
+  s = types.SimpleNamespace(fam=family(spec), has_run="no_run" not in _active, has_kinds=step_kinds(spec), has_run_pf=run_pf(spec), has_run_pf_r=run_pf_r(spec))
   wide = s.fam == "wide"
   s.step = emit_wide2 if wide else emit_small
   s.use_run2 = wide and s.has_run and tune.run2 and "no_run2" not in _active and emit_run2.applicable(spec)
@@ -499,6 +512,12 @@ def _abi_batched(spec, s):
   a.fn("int", "has_batch_run_pf", "void", f"return {int(s.has_run_pf)};")
   a.fn("int", "batch_run_pf", RUN_PF_PARAMS, _run_body(emit_small.launch_run_pf() if s.fam == "small" else emit_wide3.launch_run_pf()) if s.has_run_pf else _unsupported(
     "batch_run_pf: not generated for this model (MSCKF model, a kind with extra arguments, no fused run, or the kernel "
+    "did not fit the register file)"))
+  # The same run with a noise matrix per entry (k_run_rpf): R (T, n, zmax^2), row (t, i) the `r_per_filter != 0` row of filter i in step t.
+  a.fn("int", "has_batch_run_pf_r", "void", f"return {int(s.has_run_pf_r)};")
+  a.fn("int", "batch_run_pf_r", RUN_PF_PARAMS, _run_body(emit_small.launch_run_rpf() if s.fam == "small" else emit_wide3.launch_run_rpf(),
+                                                         r_per_entry=True) if s.has_run_pf_r else _unsupported(
+    "batch_run_pf_r: not generated for this model (MSCKF model, a kind with extra arguments, no fused run, or the kernel "
     "did not fit the register file)"))
   return a
 

@@ -467,6 +467,9 @@ __global__ __launch_bounds__(64) void k_predict(double* __restrict__ gx, double*
   if emit.run_pf(spec):            # the fused run with a schedule per filter: k_run_pf (no trace) and k_run_pf_tr (filtered trace)
     out.append(run_pf_kernel(spec, norm))
     out.append(run_pf_kernel(spec, norm, trace=True))
+  if emit.run_pf_r(spec):          # the same with a noise matrix per entry: k_run_rpf and k_run_rpf_tr
+    out.append(run_pf_kernel(spec, norm, r_entry=True))
+    out.append(run_pf_kernel(spec, norm, trace=True, r_entry=True))
   return "\n".join(out)
 
 
@@ -1124,7 +1127,18 @@ def run_pf_block(spec):
   return run_block(spec) or run_unroll(spec)
 
 
-def run_pf_kernel(spec, norm, trace=False):
+def run_pf_r_block(spec):
+  """Steps per block of k_run_rpf: run_pf_block's, halved until the rows of R of a block fit the staging registers.  The kernel stages zmax^2 more
+  doubles per step and buffer than k_run_pf (2 x K x zmax^2 on top of 2 x K x zmax: attitude at K = 8 would hold 288 VGPRs of R alone); at
+  K x zmax^2 <= 36 the rows of R take at most 144 VGPRs of the 512 a lone wavefront has.  (kinematic6 built at K = 8: 256 + 256 registers, 148 spilled
+  VGPRs and 580 B of scratch in k_run_rpf, 216 and 804 B in k_run_rpf_tr; at K = 4: 256 + 178 / 182 and none.  DESIGN.md section 12.)"""
+  K, ZZ = run_pf_block(spec), max(k.zdim for k in spec.kinds) ** 2
+  while K > 2 and K * ZZ > 36:
+    K //= 2
+  return K
+
+
+def run_pf_kernel(spec, norm, trace=False, r_entry=False):
   """The fused run with a SCHEDULE PER FILTER (kinds (T, n), dts (T, n)): N independent logs replayed in one launch.  run_kernel_blk's
   structure -- blocks of K steps in registers, ONE vmcnt(0) per block, y and the flags of block b stored at the start of block b + 1 --
   with the schedule per lane: the lane of filter i loads its own kinds[t * n + i] and dts[t * n + i] of the next block's K steps with that
@@ -1136,29 +1150,50 @@ def run_pf_kernel(spec, norm, trace=False):
   trace=True: k_run_pf_tr, every step's pair of every filter (stepped or not: the trace is dense) leaves through the LDS image as in
   k_run_blk_tr; the image of the final write-back is loaded again in front of it, since the trace has overwritten the one that came in.
 
+  r_entry=True: k_run_rpf / k_run_rpf_tr, a NOISE MATRIX PER ENTRY: gR is (T, n, zmax^2) and row (t, i) is the R of filter i's entry t (the `r_per_filter`
+  row of k_kinds).  No table in LDS: the lane of filter i stages its own rows of the next block in registers, loaded with that block's observation
+  rows and schedule under the same single wait (zmax^2 doubles per step and buffer, hence the shorter block run_pf_r_block), clamped like them at
+  rows past T and lanes past cnt.  A lane copies the leading Z^2 doubles of a row inside the case of its own kind, which an idle or flag-8 lane never
+  enters: whatever such a row and the tail of the others hold (NaN included) stays in staging registers nothing reads.
+
   The kernel's text is _blocked_run's; what is here is the schedule per lane, a register per step of the block, the table of R and `stepped`."""
   ZZ = max(k.zdim for k in spec.kinds) ** 2
   NK = len(spec.kinds)
-  K = run_pf_block(spec)
-  cases = kind_cases(spec, "_regs_sym", "cur[u]", lambda idx: f"s_R[{idx * ZZ} + i]", ind=12)
+  K = run_pf_r_block(spec) if r_entry else run_pf_block(spec)
+  cases = kind_cases(spec, "_regs_sym", "cur[u]", "Rc[u][i]" if r_entry else (lambda idx: f"s_R[{idx * ZZ} + i]"), ind=12)
   known = " ".join(f"case {k.kind}:" for k in spec.kinds)
+  if r_entry:
+    names = dict(kname="k_run_rpf_tr" if trace else "k_run_rpf", title=(
+      f"// ---- fused run, a schedule per filter and R per entry, with the filtered trace: blocks of {K} steps (see emit_small.run_pf_kernel) ----"
+      if trace else
+      f"// ---- fused run, a schedule per filter, R per entry (gR (T, n, {ZZ})): blocks of {K} steps in registers (emit_small.run_pf_kernel) ----"))
+    # the rows of R travel like the schedule: the lane's own row of every step of the block, addressed by pointer increments
+    table = dict(sched_ptrs=f"\n    const double* rrow = gR + (base + lc) * {ZZ};", decl_d=f", Rc[{K}][{ZZ}], Rn[{K}][{ZZ}]",
+                 issue_ptrs=f"\n      const double* rp_ = rrow + tb0_ * (n * {ZZ});",
+                 issue_row=f"\n#pragma unroll\n        for (int i = 0; i < {ZZ}; i++) Rn[u][i] = rp_[i];",
+                 issue_step=f"\n        rp_ += (u < left_) ? n * {ZZ} : 0;",
+                 pin_row=f"\n#pragma unroll\n        for (int i = 0; i < {ZZ}; i++) rn::pin(Rn[u][i]);",
+                 rot_row=f"\n#pragma unroll\n        for (int i = 0; i < {ZZ}; i++) Rc[u][i] = Rn[u][i];")
+  else:
+    names = dict(kname="k_run_pf_tr" if trace else "k_run_pf", title=(
+      f"// ---- fused run, a schedule per filter, with the filtered trace: blocks of {K} steps (see emit_small.run_pf_kernel) ----------------"
+      if trace else
+      f"// ---- fused run, a schedule per filter (kinds (T, n), dts (T, n)): blocks of {K} steps in registers (emit_small.run_pf_kernel) ----"),
+      lds=dict(R=NK * ZZ), fill=f"\n  for (int i = lane; i < {NK * ZZ}; i += 64) s_R[i] = gR[i];      // one row per kind, in the order of the model's kinds")
+    table = dict.fromkeys(("sched_ptrs", "decl_d", "issue_ptrs", "issue_row", "issue_step", "pin_row", "rot_row"), "")
   return _blocked_run(
-    spec, norm, trace, K, kname="k_run_pf_tr" if trace else "k_run_pf",
-    title=(f"// ---- fused run, a schedule per filter, with the filtered trace: blocks of {K} steps (see emit_small.run_pf_kernel) ----------------"
-           if trace else
-           f"// ---- fused run, a schedule per filter (kinds (T, n), dts (T, n)): blocks of {K} steps in registers (emit_small.run_pf_kernel) ----"),
-    helpers="" if trace else """
+    spec, norm, trace, K, **names,
+    helpers="" if trace or r_entry else """
 __device__ __forceinline__ void pin_k(int& v) { asm volatile("" : "+v"(v)); }
 """,
-    lds=dict(R=NK * ZZ), fill=f"\n  for (int i = lane; i < {NK * ZZ}; i += 64) s_R[i] = gR[i];      // one row per kind, in the order of the model's kinds",
     ragged_note="// lanes past the end of a ragged tile follow a copy of the last filter's schedule and rows and store nothing",
-    sched_ptrs="\n    const int32_t* krow = kinds + base + lc;\n    const double* drow = dts + base + lc;",
-    decl_d=f", dtv[{K}], dtn[{K}]", decl_i=f", kv[{K}], kn[{K}]", decl_more="\n    bool stepped = false;",
+    sched_ptrs="\n    const int32_t* krow = kinds + base + lc;\n    const double* drow = dts + base + lc;" + table["sched_ptrs"],
+    decl_d=f", dtv[{K}], dtn[{K}]" + table["decl_d"], decl_i=f", kv[{K}], kn[{K}]", decl_more="\n    bool stepped = false;",
     # the schedule is addressed by pointer increments like the rows
-    issue_ptrs="\n      const int32_t* kp_ = krow + tb0_ * n;\n      const double* dp_ = drow + tb0_ * n;",
-    issue_row="\n        kn[u] = kp_[0];\n        dtn[u] = dp_[0];",
-    issue_step="\n        kp_ += (u < left_) ? n : 0;\n        dp_ += (u < left_) ? n : 0;",
-    pin_row="\n        rn::pin(dtn[u]);\n        pin_k(kn[u]);", rot_row="\n        dtv[u] = dtn[u];\n        kv[u] = kn[u];",
+    issue_ptrs="\n      const int32_t* kp_ = krow + tb0_ * n;\n      const double* dp_ = drow + tb0_ * n;" + table["issue_ptrs"],
+    issue_row="\n        kn[u] = kp_[0];\n        dtn[u] = dp_[0];" + table["issue_row"],
+    issue_step="\n        kp_ += (u < left_) ? n : 0;\n        dp_ += (u < left_) ? n : 0;" + table["issue_step"],
+    pin_row="\n        rn::pin(dtn[u]);\n        pin_k(kn[u]);" + table["pin_row"], rot_row="\n        dtv[u] = dtn[u];\n        kv[u] = kn[u];" + table["rot_row"],
     step=f"""          const int kind = kv[u];
           int fl = 16;                             // idle entry: no predict, the row passes through
           if (kind > 0) {{
@@ -1201,6 +1236,10 @@ def _launch_blocked(kname, more=""):
 
 def launch_run_pf():
   return _launch_blocked("k_run_pf")
+
+
+def launch_run_rpf():
+  return _launch_blocked("k_run_rpf")
 
 
 def launch_run(spec=None):

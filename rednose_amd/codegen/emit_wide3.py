@@ -178,7 +178,7 @@ def predict_fn(spec, qdiag=False, pf=False):
   return "\n".join([head] + ind(b) + ["}"])
 
 
-def update_fn(spec, k, pf=False):
+def update_fn(spec, k, pf=False, r_entry=False):
   """Matrix part of the update of kind k on register rows.  y, the non-trivial entries of He = H H_mod and, for feature-track
   kinds, the Householder reflectors and the projected noise are read from the filter's slot (phase 1 put them there); dx and
   the gate / rank flags go back to it.
@@ -186,8 +186,12 @@ def update_fn(spec, k, pf=False):
   pf=True emits `update_{kind}_rows_pf` for k_run_pf, with one more argument: `mine` -- does this lane's GROUP carry this kind at this step?
   Every lane walks every statement; a group that is idle, flagged 8 or of another kind puts zeros where G and K^T go in its own buffer and
   takes zero coefficients into both rank-Z passes (row -+= 0 * 0: the rows come out unchanged, whatever stale numbers its slot holds), and
-  writes nothing into its slot."""
-  assert not (pf and k.He_sym is not None)
+  writes nothing into its slot.
+
+  r_entry=True (with pf) emits `update_{kind}_rows_rpf` for k_run_rpf, whose R is per entry: the same statements, except that `gR` is the group's OWN
+  row and its Z * Z doubles are taken only where `mine` -- the row of a group that is idle, flagged 8 or of another kind may hold anything, NaN
+  included, and such a group factors the identity instead (its coefficients are zeroed either way, but 0 * NaN is NaN)."""
+  assert not (pf and k.He_sym is not None) and (pf or not r_entry)
   E, Zf = spec.dim_err, k.zdim
   _, R, _ = layout(spec)
   lay, _, Hss, _ = w2.slot_tables(spec, RunLayout)
@@ -199,6 +203,9 @@ def update_fn(spec, k, pf=False):
   if feat:
     b += ["#pragma unroll", f"for (int i = 0; i < {Z * Z}; i++) R[i] = sl[{lay.OFF_RP} + i];      // A^T R A (phase 1)", "(void)gR;",
           f"const double rank_deficient = sl[{lay.OFF_FL}];      // 4.0 when phase 1 found Hea rank deficient"]
+  elif r_entry:
+    b += ["#pragma unroll", f"for (int i = 0; i < {Z * Z}; i++) R[i] = (i % {Z + 1} == 0) ? 1.0 : 0.0;",
+          "if (mine) {", "#pragma unroll", f"  for (int i = 0; i < {Z * Z}; i++) R[i] = gR[i];", "}"]
   else:
     b += ["#pragma unroll", f"for (int i = 0; i < {Z * Z}; i++) R[i] = gR[i];"]
   # G = He P: G[z][j] = sum_k He[z][k] P[k][j]; with P = P^T (up to the Joseph form's rounding) that is row j of P against
@@ -269,7 +276,7 @@ def update_fn(spec, k, pf=False):
   b.append("rn::wave_lds_sync();      // the broadcast buffer is free again")
   rows = ", ".join(f"double (&row{s})[{E}]" for s in range(R))
   idx = ", ".join(f"const int rr{s}, const int rc{s}, const bool ok{s}" for s in range(R))
-  head = (f"__device__ __forceinline__ void update_{k.kind}_rows{'_pf' if pf else ''}({rows}, const double* __restrict__ gR, double* sP, "
+  head = (f"__device__ __forceinline__ void update_{k.kind}_rows{('_rpf' if r_entry else '_pf') if pf else ''}({rows}, const double* __restrict__ gR, double* sP, "
           f"double* sG, const double* sl, double* sw, {idx}{', const bool mine' if pf else ''}{_tl_arg()}) {{")
   return "\n".join([head] + ind(b) + ["}"])
 
@@ -288,6 +295,8 @@ def kernels(spec, with_run=True):
   pf = []
   if emit.run_pf(spec):
     pf = [predict_fn(spec, pf=True), predict_fn(spec, qdiag=True, pf=True)] + [update_fn(spec, k, pf=True) for k in spec.kinds] + [run_pf_kernel(spec)]
+    if emit.run_pf_r(spec):      # the same with a noise matrix per entry: the updates that take R only where `mine` + k_run_rpf
+      pf += [update_fn(spec, k, pf=True, r_entry=True) for k in spec.kinds] + [run_pf_kernel(spec, r_entry=True)]
   if not with_run:
     # the model's batch_run is emit_run2's k_run2; the fused run with a schedule per filter is this module's single-wavefront structure:
     # the scalar phases against RunLayout, the predicated matrix phases and k_run_pf follow the constants
@@ -344,7 +353,7 @@ def _stamp(ph):
           "g_tl[(blockIdx.x * 64 + ti_) * 2] = __builtin_readcyclecounter(); g_tl[(blockIdx.x * 64 + ti_) * 2 + 1] = wall_clock64(); }")
 
 
-def _fused_run(spec, pf, *, title, sched, update, flags_rule, args="", unused="", pre_loop="", after_step=""):
+def _fused_run(spec, pf, *, title, sched, update, flags_rule, args="", unused="", pre_loop="", after_step="", kname=None):
   """The text of a single-wavefront fused run, once: kernel head, LDS, the tile prologue (images, slots, observations, rows into registers), the
   step loop (predict, update, inject, y and the trace out, the next observation in) and the write-back.  `pf`: a schedule per filter (k_run_pf)
   instead of a shared one (k_run) -- the predicates of the predict phase, the predicated matrix functions, the write-back into the image
@@ -399,7 +408,7 @@ def _fused_run(spec, pf, *, title, sched, update, flags_rule, args="", unused=""
   # parity-green on the device, and 8 % SLOWER: config 4 forward 23.6 ms per chunk against 21.8.)
   return f"""
 {title}
-__global__ __launch_bounds__(64) void {"k_run_pf" if pf else "k_run"}(double* __restrict__ gx, double* __restrict__ gP, const double* __restrict__ gQ,
+__global__ __launch_bounds__(64) void {kname or ("k_run_pf" if pf else "k_run")}(double* __restrict__ gx, double* __restrict__ gP, const double* __restrict__ gQ,
     const int32_t* __restrict__ kinds, const double* __restrict__ dts, const int64_t T, double* __restrict__ gz,
     const double* __restrict__ gR, const int64_t n, const int norm_quats, uint8_t* __restrict__ flags,
     double* __restrict__ tx, double* __restrict__ tP{args}) {{{unused}
@@ -565,7 +574,7 @@ def run_kernel(spec):
     after_step=aug)
 
 
-def run_pf_kernel(spec):
+def run_pf_kernel(spec, r_entry=False):
   """k_run_pf of the lane-group family: k_run's structure (GL lanes per filter, rows of P in registers, FPW filters per wavefront) with a
   SCHEDULE PER FILTER, kinds (T, n) and dts (T, n).  Every lane of a group fetches its filter's kind and dt (one address per group), a step
   ahead like the observations.  The scalar phases run on lane c == 0 of the groups that step, each on its own kind and dt.  The matrix phases
@@ -574,7 +583,13 @@ def run_pf_kernel(spec):
   groups that carry it.  An idle group (kind <= 0, flag 16) and a group whose kind the model does not have (flag 8) keep slot and rows.
   A filter that no entry stepped is not written back: the image of the final store is the one that came in, loaded again, and only the
   groups that stepped put their rows into it.  Above 32 error states a filter owns the wavefront and the tests are uniform anyway.
-  (_fused_run holds the kernel's text.)"""
+  (_fused_run holds the kernel's text.)
+
+  r_entry=True: k_run_rpf, a NOISE MATRIX PER ENTRY -- gR is (T, n, zmax^2), row (t, i) the R of filter i's entry t.  Every lane of a group reads its
+  filter's row (one address per group, like the schedule) a step ahead: the row of step t + 1 is requested once the update of step t has consumed
+  the registers, and lands under the rest of the step with the next kind, dt and observation.  The request is unconditional on a row inside the
+  buffer (group gg, the last row again at t + 1 == T); what it brings may be NaN (idle entries, entries of an unknown kind, the tail of a row), and
+  `update_{kind}_rows_rpf` takes the values only where `mine`."""
   E = spec.dim_err
   _, R, _ = layout(spec)
   lay = w2.slot_tables(spec, RunLayout)[0]
@@ -586,17 +601,34 @@ def run_pf_kernel(spec):
   scal_cases = nlc.join(f"          case {k.kind}: scal_obs_{k.kind}_r(sl, sl + {lay.OFF_Y}); break;" for k in spec.kinds)
   mat = nlc.join(f"""      {{
         const bool mine = step && kind == {k.kind};
-        if (__any(mine)) update_{k.kind}_rows_pf({rows}, gR + {i * ZZ}, sP, s_G + gg * {zmax * E}, sl, sl, {idx}, mine{_tl_arg(True)});
+        if (__any(mine)) update_{k.kind}_rows_{"rpf" if r_entry else "pf"}({rows}, {"Re" if r_entry else f"gR + {i * ZZ}"}, sP, s_G + gg * {zmax * E}, sl, sl, {idx}, mine{_tl_arg(True)});
       }}""" for i, k in enumerate(spec.kinds))
   id0_guard = "true" if not spec.identity_at_dt0() else "dt != 0.0"
+  title = f"""// ---- fused multi-step run, a schedule per filter: kinds (T, n), dts (T, n); z is (T, n, {zmax}) in: z, out: y; gR one row per kind -----------
+// k_run's phases per step; a group takes part in those its own entry asks for (see emit_wide3.run_pf_kernel)."""
+  r_first, r_next = "", ""
+  if r_entry:
+    title = f"""// ---- fused multi-step run, a schedule per filter and R per entry: kinds (T, n), dts (T, n); z is (T, n, {zmax}) in: z, out: y; gR (T, n, {ZZ}) -----------
+// k_run_pf with the group's own row of R, a step ahead in registers (see emit_wide3.run_pf_kernel)."""
+    r_first = f"""    // the group's own row of R, a step ahead like its schedule entry; taken by the updates only where the group carries their kind
+    double Re[{ZZ}];
+#pragma unroll
+    for (int i = 0; i < {ZZ}; i++) Re[i] = gR[(base + gg) * {ZZ} + i];
+"""
+    r_next = f"""
+      {{      // the update has consumed the row: the next entry's, under the rest of this step (the last row again at the end: inside the buffer)
+        const int64_t tn = t + 1 < T ? t + 1 : t;
+        const double* rp_ = gR + (tn * n + base + gg) * {ZZ};
+#pragma unroll
+        for (int i = 0; i < {ZZ}; i++) Re[i] = rp_[i];
+      }}"""
   return _fused_run(
-    spec, True, title=f"""// ---- fused multi-step run, a schedule per filter: kinds (T, n), dts (T, n); z is (T, n, {zmax}) in: z, out: y; gR one row per kind -----------
-// k_run's phases per step; a group takes part in those its own entry asks for (see emit_wide3.run_pf_kernel).""",
+    spec, True, title=title, kname="k_run_rpf" if r_entry else None,
     pre_loop="""    bool stepped = false;
     // the group's own schedule entry, a step ahead (every lane of a group reads its filter's: one address per group)
     int kind_n = kinds[base + gg];
     double dt_n = dts[base + gg];
-""",
+""" + r_first,
     sched=f"""      const int kind = live ? kind_n : 0;
       const double dt = dt_n;
       {{
@@ -615,7 +647,7 @@ def run_pf_kernel(spec):
         }}
       }}
       rn::wave_lds_sync();
-{mat}""",
+{mat}{r_next}""",
     flags_rule=f"""        int fl = kind <= 0 ? 16 : 8;          // idle entry; a kind the model does not have: untouched either way
         if (step) fl = scal_inject_r(sl, sl + {lay.OFF_X}, norm_quats) | (int)sl[{lay.OFF_FL}];""")
 
@@ -628,6 +660,10 @@ def _launch(kname, more=""):
 
 def launch_run_pf():
   return _launch("k_run_pf")
+
+
+def launch_run_rpf():
+  return _launch("k_run_rpf")
 
 
 def launch_run():

@@ -76,9 +76,16 @@ def gen_code(folder, name, f_sym, dt_sym, x_sym, obs_eqs, dim_x, dim_err, eskf_p
         # build and again behind no_run_blk, which re-emits k_run_pf with another block size -- never left to force_wide or no_run below
         pf_bad = [k for k in bad if k.startswith("k_run_pf")]
         return fall_back("no_run_pf", f"the fused run with a schedule per filter {pf_bad} does not fit the register file: library without it") if pf_bad else (usage, bad)
+      def drop_run_pf_r():
+        # likewise the same run with a noise matrix per entry ({name}_has_batch_run_pf_r() == 0): this kernel alone, k_run_pf stays
+        rpf_bad = [k for k in bad if k.startswith("k_run_rpf")]
+        return fall_back("no_run_pf_r", f"the fused run with a schedule per filter and R per entry {rpf_bad} does not fit the register file: library "
+                                        "without it") if rpf_bad else (usage, bad)
+      usage, bad = drop_run_pf_r()
       usage, bad = drop_run_pf()
       if "k_run_blk" in bad or "k_run_blk_tr" in bad:
         usage, bad = fall_back("no_run_blk", "a blocked fused run spills registers: the step-at-a-time k_run serves fused runs instead")
+        usage, bad = drop_run_pf_r()
         usage, bad = drop_run_pf()
       if bad and rn_emit.family(spec, ()) == "small":
         usage, bad = fall_back("force_wide", f"lane-per-filter kernels {bad} spill registers: regenerating in the lane-group family")
@@ -1680,6 +1687,13 @@ class BatchedEKF:
     the rows of idle entries pass through --; Rs {kind: (Z, Z)} shared by the entries of a kind.  trace / flags / out as run(): the trace is
     dense (an idle entry's row is the pair its filter had).  Returns (ys, trace_x, trace_P, flags); flags (T, N): 16 at idle entries.
 
+    The noise may also come PER ENTRY, as every predict_and_update_batch call of a recorded log brings its own R: any value of the dict may be
+    (T, N, Z, Z), read only where that kind occurs (the others stay (Z, Z)); or Rs is one tensor / array (T, N, zmax, zmax) or (T, N, zmax^2) in the
+    kernel's layout -- the first Z * Z doubles of row (t, i) are the row-major R of that entry, the rest of the row and the rows of idle entries are
+    never read and may hold anything; a contiguous float64 tensor on the device is used without a copy.  Such a run is one launch of
+    {name}_batch_run_pf_r where the library has it ({name}_has_batch_run_pf_r()); without it, or with exact=True, the step walk below takes
+    R[t] with r_per_filter = 1.  With (Z, Z) values only nothing changes: the same kernel, the same launches.  A wrong shape raises KalmanError.
+
     Every filter predicts from its own time (filter_times(); a filter that has not started takes dt = 0 on its first entry, the rule of
     batch_timeline_plan) over its own previous entry.  A log must be in time order and must not start before its filter's time: a fused run
     does not rewind -- sort the log first (stable, by time).  A kind no filter of the model has raises KeyError, as in run().  Afterwards
@@ -1711,16 +1725,11 @@ class BatchedEKF:
     if T == 0:
       return self._dev(zs, (0, N, zmax)), None, None, None
     for k in present:
-      if k not in self.zdims or k not in Rs:
+      if k not in self.zdims or (isinstance(Rs, dict) and k not in Rs):
         raise KeyError(k)
       if self.eadims.get(k, 0):
         raise KalmanError(f"run_logs: kind {k} takes extra arguments, which a per-filter schedule does not carry")
-    tab = np.zeros((len(self.kinds), zmax * zmax))
-    for i, k in enumerate(self.kinds):
-      if k in Rs:
-        Z = self.zdims[k]
-        tab[i, :Z * Z] = np.asarray(Rs[k], dtype=np.float64).reshape(Z * Z)
-    Rd = self._dev(tab)
+    Rd, per_entry = self._run_logs_noise(Rs, kd, T)
     # every entry's dt from its filter's previous entry (or the filter's time in front of the first one): a forward fill along T
     has = kd > 0
     ft0 = self.filter_times()
@@ -1746,7 +1755,12 @@ class BatchedEKF:
       tx = torch.empty((T, N, self.dim_x), dtype=torch.float64, device=self.device) if trace else None
       tP = torch.empty((T, N, self.dim_err, self.dim_err), dtype=torch.float64, device=self.device) if trace else None
     fl = torch.zeros((T, N), dtype=torch.uint8, device=self.device) if flags else None
-    if self._has_batch_run_pf() and not exact:
+    if per_entry and self._has_batch_run_pf_r() and not exact:
+      self._call("batch_run_pf_r", self._p(self.x), self._p(self.P), self._p(self.Q), self._p(kd), self._p(dts), T, self._p(zs), self._p(Rd), N,
+                 self.norm_quats, self._p(fl), self._p(tx), self._p(tP), self._stream())
+    elif per_entry:
+      self._run_logs_stepwise(kd, dts, zs, Rd, fl, tx, tP, symmetrise=not exact, per_entry=True)
+    elif self._has_batch_run_pf() and not exact:
       self._call("batch_run_pf", self._p(self.x), self._p(self.P), self._p(self.Q), self._p(kd), self._p(dts), T, self._p(zs), self._p(Rd), N,
                  self.norm_quats, self._p(fl), self._p(tx), self._p(tP), self._stream())
     else:
@@ -1758,8 +1772,56 @@ class BatchedEKF:
     self._keepalive = (kd, dts, Rd)
     return zs, tx, tP, fl
 
-  def _run_logs_stepwise(self, kd, dts, zs, Rd, fl, tx, tP, symmetrise=True):
-    """run_logs() for a library without the fused kernel, and run_logs(exact=True): the same per-filter schedule, step by step."""
+  def _has_batch_run_pf_r(self):
+    fn = getattr(self._lib, f"{self.name}_has_batch_run_pf_r", None)
+    return fn is not None and int(fn()) == 1
+
+  def _run_logs_noise(self, Rs, kd, T):
+    """The observation noise of run_logs() on the device -> (Rd, per_entry).  Shared by the entries of every kind: the per-kind table
+    (num_kinds, zmax^2) of batch_run_pf, per_entry False.  Otherwise the kernel's per-entry layout (T, N, zmax^2) of batch_run_pf_r: row (t, i)
+    starts with the row-major (Z, Z) of entry (t, i).  A tensor or array in that layout is taken as it is (a device tensor of the right dtype
+    without a copy); a dict is gathered into it, every kind's rows where that kind occurs."""
+    torch = self._torch
+    N, zmax = self.batch, max(self.zdims.values())
+    ZZ = zmax * zmax
+    if not isinstance(Rs, dict):
+      shape = tuple(Rs.shape) if hasattr(Rs, "shape") else np.shape(Rs)
+      if shape not in ((T, N, zmax, zmax), (T, N, ZZ)):
+        raise KalmanError(f"run_logs: Rs as one array is per entry, (T, N, zmax, zmax) = ({T}, {N}, {zmax}, {zmax}) or (T, N, zmax^2) = ({T}, {N}, {ZZ}), "
+                          f"got {shape}")
+      return self._dev(Rs).reshape(T, N, ZZ), True
+    shared, entry = {}, {}
+    for k in self.kinds:
+      if k not in Rs:
+        continue
+      Z = self.zdims[k]
+      shape = tuple(Rs[k].shape) if hasattr(Rs[k], "shape") else np.shape(Rs[k])
+      if len(shape) == 4:
+        if shape != (T, N, Z, Z):
+          raise KalmanError(f"run_logs: Rs[{k}] per entry must be (T, N, Z, Z) = ({T}, {N}, {Z}, {Z}), got {shape}")
+        entry[k] = Rs[k]
+      else:
+        if int(np.prod(shape)) != Z * Z:
+          raise KalmanError(f"run_logs: Rs[{k}] must be (Z, Z) = ({Z}, {Z}), or (T, N, Z, Z) = ({T}, {N}, {Z}, {Z}) per entry, got {shape}")
+        v = Rs[k].detach().cpu().numpy() if isinstance(Rs[k], torch.Tensor) else Rs[k]
+        shared[k] = np.asarray(v, dtype=np.float64).reshape(Z * Z)
+    if not entry:
+      tab = np.zeros((len(self.kinds), ZZ))
+      for i, k in enumerate(self.kinds):
+        if k in shared:
+          tab[i, :self.zdims[k] ** 2] = shared[k]
+      return self._dev(tab), False
+    Rd = torch.zeros((T, N, ZZ), dtype=torch.float64, device=self.device)
+    for k in self.kinds:      # a kind's values are read only where that kind occurs
+      if k in shared or k in entry:
+        Z2 = self.zdims[k] ** 2
+        v = self._dev(entry[k]).reshape(T, N, Z2) if k in entry else self._dev(shared[k]).expand(T, N, Z2)
+        Rd[:, :, :Z2] = torch.where((kd == k)[:, :, None], v, Rd[:, :, :Z2])
+    return Rd, True
+
+  def _run_logs_stepwise(self, kd, dts, zs, Rd, fl, tx, tP, symmetrise=True, per_entry=False):
+    """run_logs() for a library without the fused kernel, and run_logs(exact=True): the same per-filter schedule, step by step.
+    per_entry: Rd is (T, N, zmax^2), and step t takes Rd[t] with r_per_filter = 1 (the `_masked` walk: that kind's rows compacted to (N, Z^2))."""
     torch = self._torch
     T, N = kd.shape
     mixed = self._has_step_kinds()
@@ -1775,19 +1837,24 @@ class BatchedEKF:
       zt = zs[t].clone()                   # own allocation: the C ABI wants 16-byte aligned observations
       if mixed:
         kt = kd[t].clone()
-        self._call("batch_predict_update_kinds", self._p(self.x), self._p(self.P), self._p(self.Q), self._p(dt), 0.0, self._p(kt), self._p(zt), self._p(Rd), 0,
-                   N, self.norm_quats, self._p(flt), self._p(a8), self._stream())
-        keep = [(kt, a8, dt, zt)]      # (the stream orders the launches: the previous step's buffers may go)
+        Rt = Rd[t].clone() if per_entry else Rd          # (own allocation, like zt)
+        self._call("batch_predict_update_kinds", self._p(self.x), self._p(self.P), self._p(self.Q), self._p(dt), 0.0, self._p(kt), self._p(zt), self._p(Rt),
+                   int(per_entry), N, self.norm_quats, self._p(flt), self._p(a8), self._stream())
+        keep = [(kt, a8, dt, zt, Rt)]      # (the stream orders the launches: the previous step's buffers may go)
       else:
         flt.fill_(16)
         for k in (int(k_) for k_ in np.unique(kh[t]) if int(k_) > 0):
           Z = self.zdims[k]
           m8 = (kd[t] == k).to(torch.uint8)
           zk = zt[:, :Z].contiguous()
-          Rk = Rd[self.kinds.index(k), :Z * Z].clone()
+          if per_entry:      # this kind's rows; the identity where a filter brings another kind or none (its row may hold anything)
+            eye = torch.eye(Z, dtype=torch.float64, device=self.device).reshape(1, Z * Z)
+            Rk = torch.where(m8[:, None] != 0, Rd[t, :, :Z * Z], eye).contiguous()
+          else:
+            Rk = Rd[self.kinds.index(k), :Z * Z].clone()
           fk = torch.zeros(N, dtype=torch.uint8, device=self.device)
-          self._call(f"batch_predict_update_{k}_masked", self._p(self.x), self._p(self.P), self._p(self.Q), self._p(dt), 0.0, self._p(zk), self._p(Rk), 0,
-                     None, N, self.norm_quats, self._p(fk), self._p(m8), self._stream())
+          self._call(f"batch_predict_update_{k}_masked", self._p(self.x), self._p(self.P), self._p(self.Q), self._p(dt), 0.0, self._p(zk), self._p(Rk),
+                     int(per_entry), None, N, self.norm_quats, self._p(fk), self._p(m8), self._stream())
           zt[:, :Z] = torch.where(m8[:, None] != 0, zk, zt[:, :Z])
           flt.copy_(torch.where(m8 != 0, fk, flt))
           keep = keep[-len(self.kinds):] + [(m8, zk, Rk, fk, dt)]
