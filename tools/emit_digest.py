@@ -28,6 +28,8 @@ LANE_GROUP_KNOBS = {      # of the lane-group family: the branches of its step k
   "kinematic9": ("wide_fpw=2", "wide_db=1", "wide_lean=1", "wide_lean=1,wide_lean_q=1", "wide_ft=8,wide_lb=2"),
   "rand13": ("wide_timeline=1",), "rand17": ("wide_timeline=1",), "rand24": ("wide_timeline=1",),
   "feature": ("wide_lean=1",), "feature36": ("wide_ft=8",), "randz10": ("wide_lean=1",)}
+# of the smoother k_rts4: with those above, full and packed x odd and even records x with and without the identity-gain step (appended at the end)
+RTS4_KNOBS = {"rand17": ("rts_dt0=0", "tri_trace=0"), "kinematic9": ("rts_dt0=0",), "rand8": ("rts_dt0=0",)}
 
 
 def configurations():
@@ -40,7 +42,8 @@ def configurations():
   cfg += [(n, kn, None) for n in ("kinematic6", "attitude") for kn in KNOBS] + [("kinematic9", "wide_timeline=1", None)]
   cfg += [(n, "", None) for n in GV_MODELS]      # appended to, never reordered: earlier digest files stay a prefix of later ones
   cfg += [(n, kn, None) for n, knobs in LANE_GROUP_KNOBS.items() for kn in knobs]
-  return cfg + [(n, kn, None) for n in ("kinematic6", "attitude") for kn in HEAD_KNOBS]
+  cfg += [(n, kn, None) for n in ("kinematic6", "attitude") for kn in HEAD_KNOBS]
+  return cfg + [(n, kn, None) for n, knobs in RTS4_KNOBS.items() for kn in knobs]
 
 
 def gv_spec(name):
