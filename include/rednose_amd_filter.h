@@ -335,6 +335,26 @@ extern "C" {
                                   int64_t T, double *z, const double *R, int64_t n, int norm_quats,               \
                                   uint8_t *flags, double *trace_x, double *trace_P, void *stream);
 
+/* THE SAME RUN WITH A DIAGONAL NOISE PER LOG ENTRY.  The noise a recorded log carries is almost always diagonal (np.diag(std**2), a
+ * variance per component); as full (Z, Z) matrices it costs batch_run_pf_r Z * Z doubles per entry where Z would do.  Here every entry
+ * (t, i) brings the Z variances of its observation.
+ *   {name}_has_batch_run_pf_rd() == 1: the library has the kernel.  0: a library without batch_run_pf, or one whose kernel did not fit the
+ *   register file -- batch_run_pf_rd then returns status 4 and nothing is launched (expand the rows to (Z, Z) matrices and call
+ *   batch_run_pf_r, or walk the schedule as described there).  Not tied to has_batch_run_pf_r(): a row is zmax doubles, not zmax * zmax.
+ * Every argument is batch_run_pf_r's, and so are the status codes, the argument checks (NULL -> 2, misaligned -> 3, T == 0 or n == 0 a
+ * no-op that returns 0, no device -> 1), the alignment rules, the flag rules 16 / 8, the dense trace, (P + P^T) / 2 at entry, and "a filter
+ * that no entry stepped is not written back".  What differs is R:
+ *   R is a DEVICE array (T, n, zmax), 16-byte aligned at its base.  The leading Z doubles of row (t, i) are the diagonal of the noise of
+ *   entry (t, i) -- variances, positive --, Z being the Z of kinds[t, i]; the off-diagonal entries are zero by definition.  The rest of a
+ *   row is never read, and neither are the rows of idle entries (kinds[t, i] <= 0) and of entries with an unknown kind (flag 8): such
+ *   doubles may hold anything, NaN included, and nothing of them reaches x, P, y, the flags or the trace.
+ * The run is batch_run_pf_r on the matrices diag(row), to rounding. */
+#define RN_DECLARE_BATCH_RUN_PF_RD(name)                                                                          \
+  int RN_FN(name, has_batch_run_pf_rd)(void);                                                                     \
+  int RN_FN(name, batch_run_pf_rd)(double *x, double *P, const double *Q, const int32_t *kinds, const double *dts, \
+                                   int64_t T, double *z, const double *R, int64_t n, int norm_quats,               \
+                                   uint8_t *flags, double *trace_x, double *trace_P, void *stream);
+
 /* Per-filter timelines, THE LATE OBSERVATION ON THE DEVICE: the rewind of every filter batch_timeline_plan found late, each in its own ring
  * (EKF_sym.rewind and the too-old test in front of it, the reference's ekf_sym.py:418-438, 464-471), and the gather of the
  * overtaken entries, one replay position of all rewound filters at a time, into the buffers batch_predict_update_kinds and

@@ -50,8 +50,10 @@ SMALL_MAX_E = 7    # lane-per-filter register budget: x, P and the update's temp
 #                      ({name}_has_batch_run_pf() == 0, batch_run_pf returns ERR_UNSUPPORTED; BatchedEKF.run_logs walks such logs step by step)
 #   no_run_pf_r        the fused run with a schedule per filter and a noise matrix per entry (k_run_rpf / k_run_rpf_tr) touches scratch memory or spills ->
 #                      library without it ({name}_has_batch_run_pf_r() == 0, batch_run_pf_r returns ERR_UNSUPPORTED); k_run_pf and everything else stay
+#   no_run_pf_rd       the same run with a DIAGONAL noise per entry (k_run_dpf / k_run_dpf_tr) touches scratch memory or spills -> library without it
+#                      ({name}_has_batch_run_pf_rd() == 0, batch_run_pf_rd returns ERR_UNSUPPORTED); k_run_pf, k_run_rpf and everything else stay
 FALLBACKS = ("force_wide", "no_model_defaults", "no_rts4", "rts_one_wave", "no_rts", "no_run2", "no_run", "no_run_blk", "no_tri", "no_kinds", "no_run_pf",
-             "no_run_pf_r")
+             "no_run_pf_r", "no_run_pf_rd")
 KINDS_MAX = 16      # kinds of a model with a mixed-kind step: the Z table rn::k_timeline_push takes by value
 _active = frozenset()      # fallbacks of the emit() call in progress
 
@@ -89,6 +91,13 @@ def run_pf_r(spec, fallbacks=None):
   emit_wide3.run_rpf_kernel)?  At most where run_pf() is."""
   fb = _active if fallbacks is None else fallbacks
   return "no_run_pf_r" not in fb and run_pf(spec, fb)
+
+
+def run_pf_rd(spec, fallbacks=None):
+  """Does this library get the fused run with a schedule per filter and a DIAGONAL noise per entry (k_run_dpf: emit_small.run_pf_kernel,
+  emit_wide3.run_pf_kernel with r_diag)?  At most where run_pf() is; not tied to run_pf_r(): a row is zmax doubles where k_run_rpf's is zmax^2."""
+  fb = _active if fallbacks is None else fallbacks
+  return "no_run_pf_rd" not in fb and run_pf(spec, fb)
 
 
 def _align2(n):
@@ -184,7 +193,7 @@ RTS_PARAMS = ("const double *xf, const double *Pf, const double *ts, int64_t T, 
 
 
 def _run_body(launch, hip_check=True, r_per_entry=False):
-  """r_per_entry: R is (T, n, zmax^2) (batch_run_pf_r), read by the lanes and 16-byte aligned like x, P and z."""
+  """r_per_entry: R is (T, n, zmax^2) (batch_run_pf_r) or (T, n, zmax) (batch_run_pf_rd), read by the lanes and 16-byte aligned like x, P and z."""
   return _batched("n >= 0 && T >= 0 && x && P && Q && kinds && dts && z && R", ["x", "P", "z", "trace_x", "trace_P"] + (["R per entry"] if r_per_entry else []),
                   launch, empty="n == 0 || T == 0", hip_check=hip_check)
 
@@ -203,11 +212,12 @@ def _select(spec):
               larger models, and the fallback of k_rts4)
     use_tri   packed-triangle trace: both structures or neither (batch_run_tri writes what batch_rts_tri reads)
     has_kinds the mixed-kind step kernel k_kinds;  has_run_pf: the fused run with a schedule per filter (k_run_pf);  has_run_pf_r: the same with a
-              noise matrix per entry (k_run_rpf)"""
+              noise matrix per entry (k_run_rpf);  has_run_pf_rd: with a diagonal noise per entry (k_run_dpf)"""
   if spec.dim_err > 64:
     raise NotImplementedError(f"{spec.dim_err} error states: the lane-group kernels hold one row of P per lane of a wavefront (<= 64)")
   tune = tuning.current()
-  s = types.SimpleNamespace(fam=family(spec), has_run="no_run" not in _active, has_kinds=step_kinds(spec), has_run_pf=run_pf(spec), has_run_pf_r=run_pf_r(spec))
+  s = types.SimpleNamespace(fam=family(spec), has_run="no_run" not in _active, has_kinds=step_kinds(spec), has_run_pf=run_pf(spec), has_run_pf_r=run_pf_r(spec),
+                            has_run_pf_rd=run_pf_rd(spec))
   wide = s.fam == "wide"
   s.step = emit_wide2 if wide else emit_small
   s.use_run2 = wide and s.has_run and tune.run2 and "no_run2" not in _active and emit_run2.applicable(spec)
@@ -518,6 +528,12 @@ def _abi_batched(spec, s):
   a.fn("int", "batch_run_pf_r", RUN_PF_PARAMS, _run_body(emit_small.launch_run_rpf() if s.fam == "small" else emit_wide3.launch_run_rpf(),
                                                          r_per_entry=True) if s.has_run_pf_r else _unsupported(
     "batch_run_pf_r: not generated for this model (MSCKF model, a kind with extra arguments, no fused run, or the kernel "
+    "did not fit the register file)"))
+  # The same run with a diagonal noise per entry (k_run_dpf): R (T, n, zmax), the leading Z doubles of row (t, i) the variances of filter i's entry t.
+  a.fn("int", "has_batch_run_pf_rd", "void", f"return {int(s.has_run_pf_rd)};")
+  a.fn("int", "batch_run_pf_rd", RUN_PF_PARAMS, _run_body(emit_small.launch_run_dpf() if s.fam == "small" else emit_wide3.launch_run_dpf(),
+                                                          r_per_entry=True) if s.has_run_pf_rd else _unsupported(
+    "batch_run_pf_rd: not generated for this model (MSCKF model, a kind with extra arguments, no fused run, or the kernel "
     "did not fit the register file)"))
   return a
 

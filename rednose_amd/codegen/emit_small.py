@@ -470,6 +470,9 @@ __global__ __launch_bounds__(64) void k_predict(double* __restrict__ gx, double*
   if emit.run_pf_r(spec):          # the same with a noise matrix per entry: k_run_rpf and k_run_rpf_tr
     out.append(run_pf_kernel(spec, norm, r_entry=True))
     out.append(run_pf_kernel(spec, norm, trace=True, r_entry=True))
+  if emit.run_pf_rd(spec):         # the same with a diagonal noise per entry: k_run_dpf and k_run_dpf_tr
+    out.append(run_pf_kernel(spec, norm, r_diag=True))
+    out.append(run_pf_kernel(spec, norm, trace=True, r_diag=True))
   return "\n".join(out)
 
 
@@ -1138,7 +1141,20 @@ def run_pf_r_block(spec):
   return K
 
 
-def run_pf_kernel(spec, norm, trace=False, r_entry=False):
+def run_pf_rd_block(spec):
+  """Steps per block of k_run_dpf: run_pf_block's, halved while the diagonal rows of a block exceed the staging budget run_pf_r_block states
+  (K x zmax <= 36 doubles per buffer), or while the rows of both buffers with x and P take more than 172 VGPRs: what kinematic6's k_run_pf_tr
+  (256 + 168 registers at K = 8, 84 of them x and P) leaves of the 512 a lone wavefront has.  kinematic6 built at K = 8 (96 VGPRs of rows): k_run_dpf
+  256 + 218 and none spilled, k_run_dpf_tr 256 + 256 with 6 spilled VGPRs and 28 B of scratch; at K = 4 both fit.  A row is zmax doubles, not
+  zmax^2: kinematic keeps 16, the 3- and 5-state models their 4, the 6-state models take 4 of k_run_pf's 8 like k_run_rpf.  The register table
+  decides, not this rule: DESIGN.md section 12."""
+  K, zmax = run_pf_block(spec), max(k.zdim for k in spec.kinds)
+  while K > 2 and (K * zmax > 36 or 4 * K * zmax + 2 * (spec.dim_x + spec.dim_err ** 2) > 172):
+    K //= 2
+  return K
+
+
+def run_pf_kernel(spec, norm, trace=False, r_entry=False, r_diag=False):
   """The fused run with a SCHEDULE PER FILTER (kinds (T, n), dts (T, n)): N independent logs replayed in one launch.  run_kernel_blk's
   structure -- blocks of K steps in registers, ONE vmcnt(0) per block, y and the flags of block b stored at the start of block b + 1 --
   with the schedule per lane: the lane of filter i loads its own kinds[t * n + i] and dts[t * n + i] of the next block's K steps with that
@@ -1156,17 +1172,35 @@ def run_pf_kernel(spec, norm, trace=False, r_entry=False):
   rows past T and lanes past cnt.  A lane copies the leading Z^2 doubles of a row inside the case of its own kind, which an idle or flag-8 lane never
   enters: whatever such a row and the tail of the others hold (NaN included) stays in staging registers nothing reads.
 
+  r_diag=True: k_run_dpf / k_run_dpf_tr, a DIAGONAL NOISE PER ENTRY: k_run_rpf's structure with rows of zmax doubles -- gR is (T, n, zmax), the leading Z
+  doubles of row (t, i) the variances of filter i's entry t.  Staged, clamped and waited for exactly like k_run_rpf's rows (a third of the registers
+  at zmax = 3; the block is run_pf_rd_block's).  Inside the case of its own kind a lane fills the update's
+  Rk[Z * Z] with its Z variances on the diagonal and literal zeros elsewhere; the update's statements are those of the other two kernels.
+
   The kernel's text is _blocked_run's; what is here is the schedule per lane, a register per step of the block, the table of R and `stepped`."""
-  ZZ = max(k.zdim for k in spec.kinds) ** 2
+  assert not (r_entry and r_diag)
+  zmax = max(k.zdim for k in spec.kinds)
+  ZZ = zmax ** 2
   NK = len(spec.kinds)
-  K = run_pf_r_block(spec) if r_entry else run_pf_block(spec)
-  cases = kind_cases(spec, "_regs_sym", "cur[u]", "Rc[u][i]" if r_entry else (lambda idx: f"s_R[{idx * ZZ} + i]"), ind=12)
+  K = run_pf_r_block(spec) if r_entry else run_pf_rd_block(spec) if r_diag else run_pf_block(spec)
+  if r_diag:      # Rk of a kind: its Z variances on the diagonal (i a constant of the unrolled loop)
+    r_expr = lambda idx: f"(i % {spec.kinds[idx].zdim + 1} == 0) ? Rc[u][i / {spec.kinds[idx].zdim + 1}] : 0.0"
+  else:
+    r_expr = "Rc[u][i]" if r_entry else (lambda idx: f"s_R[{idx * ZZ} + i]")
+  cases = kind_cases(spec, "_regs_sym", "cur[u]", r_expr, ind=12)
   known = " ".join(f"case {k.kind}:" for k in spec.kinds)
-  if r_entry:
-    names = dict(kname="k_run_rpf_tr" if trace else "k_run_rpf", title=(
-      f"// ---- fused run, a schedule per filter and R per entry, with the filtered trace: blocks of {K} steps (see emit_small.run_pf_kernel) ----"
-      if trace else
-      f"// ---- fused run, a schedule per filter, R per entry (gR (T, n, {ZZ})): blocks of {K} steps in registers (emit_small.run_pf_kernel) ----"))
+  if r_entry or r_diag:
+    if r_diag:
+      ZZ = zmax      # doubles per row of gR
+      names = dict(kname="k_run_dpf_tr" if trace else "k_run_dpf", title=(
+        f"// ---- fused run, a schedule per filter and a diagonal R per entry, with the filtered trace: blocks of {K} steps (see emit_small.run_pf_kernel) ----"
+        if trace else
+        f"// ---- fused run, a schedule per filter, diagonal R per entry (gR (T, n, {ZZ})): blocks of {K} steps in registers (emit_small.run_pf_kernel) ----"))
+    else:
+      names = dict(kname="k_run_rpf_tr" if trace else "k_run_rpf", title=(
+        f"// ---- fused run, a schedule per filter and R per entry, with the filtered trace: blocks of {K} steps (see emit_small.run_pf_kernel) ----"
+        if trace else
+        f"// ---- fused run, a schedule per filter, R per entry (gR (T, n, {ZZ})): blocks of {K} steps in registers (emit_small.run_pf_kernel) ----"))
     # the rows of R travel like the schedule: the lane's own row of every step of the block, addressed by pointer increments
     table = dict(sched_ptrs=f"\n    const double* rrow = gR + (base + lc) * {ZZ};", decl_d=f", Rc[{K}][{ZZ}], Rn[{K}][{ZZ}]",
                  issue_ptrs=f"\n      const double* rp_ = rrow + tb0_ * (n * {ZZ});",
@@ -1183,7 +1217,7 @@ def run_pf_kernel(spec, norm, trace=False, r_entry=False):
     table = dict.fromkeys(("sched_ptrs", "decl_d", "issue_ptrs", "issue_row", "issue_step", "pin_row", "rot_row"), "")
   return _blocked_run(
     spec, norm, trace, K, **names,
-    helpers="" if trace or r_entry else """
+    helpers="" if trace or r_entry or r_diag else """
 __device__ __forceinline__ void pin_k(int& v) { asm volatile("" : "+v"(v)); }
 """,
     ragged_note="// lanes past the end of a ragged tile follow a copy of the last filter's schedule and rows and store nothing",
@@ -1240,6 +1274,10 @@ def launch_run_pf():
 
 def launch_run_rpf():
   return _launch_blocked("k_run_rpf")
+
+
+def launch_run_dpf():
+  return _launch_blocked("k_run_dpf")
 
 
 def launch_run(spec=None):

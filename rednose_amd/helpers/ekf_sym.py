@@ -81,10 +81,17 @@ def gen_code(folder, name, f_sym, dt_sym, x_sym, obs_eqs, dim_x, dim_err, eskf_p
         rpf_bad = [k for k in bad if k.startswith("k_run_rpf")]
         return fall_back("no_run_pf_r", f"the fused run with a schedule per filter and R per entry {rpf_bad} does not fit the register file: library "
                                         "without it") if rpf_bad else (usage, bad)
+      def drop_run_pf_rd():
+        # and the one with a diagonal noise per entry ({name}_has_batch_run_pf_rd() == 0): this kernel alone, k_run_pf and k_run_rpf stay
+        dpf_bad = [k for k in bad if k.startswith("k_run_dpf")]
+        return fall_back("no_run_pf_rd", f"the fused run with a schedule per filter and a diagonal R per entry {dpf_bad} does not fit the register file: "
+                                         "library without it") if dpf_bad else (usage, bad)
+      usage, bad = drop_run_pf_rd()
       usage, bad = drop_run_pf_r()
       usage, bad = drop_run_pf()
       if "k_run_blk" in bad or "k_run_blk_tr" in bad:
         usage, bad = fall_back("no_run_blk", "a blocked fused run spills registers: the step-at-a-time k_run serves fused runs instead")
+        usage, bad = drop_run_pf_rd()
         usage, bad = drop_run_pf_r()
         usage, bad = drop_run_pf()
       if bad and rn_emit.family(spec, ()) == "small":
@@ -1694,6 +1701,15 @@ class BatchedEKF:
     {name}_batch_run_pf_r where the library has it ({name}_has_batch_run_pf_r()); without it, or with exact=True, the step walk below takes
     R[t] with r_per_filter = 1.  With (Z, Z) values only nothing changes: the same kernel, the same launches.  A wrong shape raises KalmanError.
 
+    A per-entry noise that is DIAGONAL -- np.diag(std**2), what recorded logs carry -- comes as its variances: a dict value (T, N, Z), read only
+    where that kind occurs, or one tensor / array (T, N, zmax) whose row (t, i) starts with the Z variances of that entry (the rest of the row and
+    the rows of idle entries are never read and may hold anything; a contiguous float64 tensor on the device is used without a copy; with
+    zmax == 1 that shape is (T, N, zmax^2) above: the same numbers, that path).  A dict takes ONE launch of {name}_batch_run_pf_rd (rows of zmax
+    doubles in place of zmax^2) where the library has it ({name}_has_batch_run_pf_rd()), exact is false, no value is (T, N, Z, Z) and every
+    shared (Z, Z) value is exactly diagonal (its diagonal fills the rows of its kind); the array under the first two conditions.  Otherwise the
+    variances are expanded to full matrices in the layout (T, N, zmax^2) and take the path of the paragraph above.  (A three-dimensional dict
+    value of Z * Z elements is the shared (Z, Z) it always was: a log with T * N == Z goes as the array or as (T, N, Z, Z).)
+
     Every filter predicts from its own time (filter_times(); a filter that has not started takes dt = 0 on its first entry, the rule of
     batch_timeline_plan) over its own previous entry.  A log must be in time order and must not start before its filter's time: a fused run
     does not rewind -- sort the log first (stable, by time).  A kind no filter of the model has raises KeyError, as in run().  Afterwards
@@ -1729,7 +1745,7 @@ class BatchedEKF:
         raise KeyError(k)
       if self.eadims.get(k, 0):
         raise KalmanError(f"run_logs: kind {k} takes extra arguments, which a per-filter schedule does not carry")
-    Rd, per_entry = self._run_logs_noise(Rs, kd, T)
+    Rd, per_entry = self._run_logs_noise(Rs, kd, T, diag_ok=self._has_batch_run_pf_rd() and not exact)
     # every entry's dt from its filter's previous entry (or the filter's time in front of the first one): a forward fill along T
     has = kd > 0
     ft0 = self.filter_times()
@@ -1755,7 +1771,10 @@ class BatchedEKF:
       tx = torch.empty((T, N, self.dim_x), dtype=torch.float64, device=self.device) if trace else None
       tP = torch.empty((T, N, self.dim_err, self.dim_err), dtype=torch.float64, device=self.device) if trace else None
     fl = torch.zeros((T, N), dtype=torch.uint8, device=self.device) if flags else None
-    if per_entry and self._has_batch_run_pf_r() and not exact:
+    if per_entry == "diag":      # (only with the kernel and exact false: _run_logs_noise expands the variances otherwise)
+      self._call("batch_run_pf_rd", self._p(self.x), self._p(self.P), self._p(self.Q), self._p(kd), self._p(dts), T, self._p(zs), self._p(Rd), N,
+                 self.norm_quats, self._p(fl), self._p(tx), self._p(tP), self._stream())
+    elif per_entry and self._has_batch_run_pf_r() and not exact:
       self._call("batch_run_pf_r", self._p(self.x), self._p(self.P), self._p(self.Q), self._p(kd), self._p(dts), T, self._p(zs), self._p(Rd), N,
                  self.norm_quats, self._p(fl), self._p(tx), self._p(tP), self._stream())
     elif per_entry:
@@ -1776,21 +1795,46 @@ class BatchedEKF:
     fn = getattr(self._lib, f"{self.name}_has_batch_run_pf_r", None)
     return fn is not None and int(fn()) == 1
 
-  def _run_logs_noise(self, Rs, kd, T):
+  def _has_batch_run_pf_rd(self):
+    fn = getattr(self._lib, f"{self.name}_has_batch_run_pf_rd", None)
+    return fn is not None and int(fn()) == 1
+
+  def _run_logs_noise(self, Rs, kd, T, diag_ok=False):
     """The observation noise of run_logs() on the device -> (Rd, per_entry).  Shared by the entries of every kind: the per-kind table
     (num_kinds, zmax^2) of batch_run_pf, per_entry False.  Otherwise the kernel's per-entry layout (T, N, zmax^2) of batch_run_pf_r: row (t, i)
-    starts with the row-major (Z, Z) of entry (t, i).  A tensor or array in that layout is taken as it is (a device tensor of the right dtype
-    without a copy); a dict is gathered into it, every kind's rows where that kind occurs."""
+    starts with the row-major (Z, Z) of entry (t, i), per_entry True.  A tensor or array in that layout is taken as it is (a device tensor of the
+    right dtype without a copy); a dict is gathered into it, every kind's rows where that kind occurs.
+    Variances per entry -- a dict value (T, N, Z), or one array (T, N, zmax) -- stay rows of zmax doubles, the layout of batch_run_pf_rd, and
+    per_entry is "diag", where diag_ok (the library has that kernel and the run is not exact) and nothing in the dict needs a full matrix (no
+    (T, N, Z, Z) value, every shared value exactly diagonal); otherwise they are expanded into the (T, N, zmax^2) layout, per_entry True."""
     torch = self._torch
     N, zmax = self.batch, max(self.zdims.values())
     ZZ = zmax * zmax
+
+    def embed(v, Z):      # variances (T, N, Z) -> row-major diag(v) (T, N, Z * Z)
+      return torch.diag_embed(v).reshape(T, N, Z * Z)
+
+    def gather(width, rows):      # (T, N, width): rows(k) (T, N, w_k) where kind k occurs (a kind's values are read only there), zeros elsewhere
+      Rd = torch.zeros((T, N, width), dtype=torch.float64, device=self.device)
+      for k in self.kinds:
+        v = rows(k)
+        if v is not None:
+          w = v.shape[2]
+          Rd[:, :, :w] = torch.where((kd == k)[:, :, None], v, Rd[:, :, :w])
+      return Rd
+
     if not isinstance(Rs, dict):
       shape = tuple(Rs.shape) if hasattr(Rs, "shape") else np.shape(Rs)
+      if shape == (T, N, zmax) and zmax > 1:
+        var = self._dev(Rs)
+        if diag_ok:
+          return var, "diag"
+        return gather(ZZ, lambda k: embed(var[:, :, :self.zdims[k]], self.zdims[k])), True
       if shape not in ((T, N, zmax, zmax), (T, N, ZZ)):
         raise KalmanError(f"run_logs: Rs as one array is per entry, (T, N, zmax, zmax) = ({T}, {N}, {zmax}, {zmax}) or (T, N, zmax^2) = ({T}, {N}, {ZZ}), "
-                          f"got {shape}")
+                          f"or its variances (T, N, zmax) = ({T}, {N}, {zmax}), got {shape}")
       return self._dev(Rs).reshape(T, N, ZZ), True
-    shared, entry = {}, {}
+    shared, entry, var = {}, {}, {}
     for k in self.kinds:
       if k not in Rs:
         continue
@@ -1800,24 +1844,26 @@ class BatchedEKF:
         if shape != (T, N, Z, Z):
           raise KalmanError(f"run_logs: Rs[{k}] per entry must be (T, N, Z, Z) = ({T}, {N}, {Z}, {Z}), got {shape}")
         entry[k] = Rs[k]
+      elif shape == (T, N, Z) and T * N != Z:
+        var[k] = Rs[k]
       else:
         if int(np.prod(shape)) != Z * Z:
-          raise KalmanError(f"run_logs: Rs[{k}] must be (Z, Z) = ({Z}, {Z}), or (T, N, Z, Z) = ({T}, {N}, {Z}, {Z}) per entry, got {shape}")
+          raise KalmanError(f"run_logs: Rs[{k}] must be (Z, Z) = ({Z}, {Z}), or (T, N, Z, Z) = ({T}, {N}, {Z}, {Z}) per entry, "
+                            f"or that entry's variances (T, N, Z) = ({T}, {N}, {Z}), got {shape}")
         v = Rs[k].detach().cpu().numpy() if isinstance(Rs[k], torch.Tensor) else Rs[k]
         shared[k] = np.asarray(v, dtype=np.float64).reshape(Z * Z)
-    if not entry:
+    if not entry and not var:
       tab = np.zeros((len(self.kinds), ZZ))
       for i, k in enumerate(self.kinds):
         if k in shared:
           tab[i, :self.zdims[k] ** 2] = shared[k]
       return self._dev(tab), False
-    Rd = torch.zeros((T, N, ZZ), dtype=torch.float64, device=self.device)
-    for k in self.kinds:      # a kind's values are read only where that kind occurs
-      if k in shared or k in entry:
-        Z2 = self.zdims[k] ** 2
-        v = self._dev(entry[k]).reshape(T, N, Z2) if k in entry else self._dev(shared[k]).expand(T, N, Z2)
-        Rd[:, :, :Z2] = torch.where((kd == k)[:, :, None], v, Rd[:, :, :Z2])
-    return Rd, True
+    if var and not entry and diag_ok and all(not (m - np.diag(np.diag(m))).any() for m in (shared[k].reshape(self.zdims[k], -1) for k in shared)):
+      return gather(zmax, lambda k: self._dev(var[k]) if k in var else
+                    self._dev(shared[k][::self.zdims[k] + 1].copy()).expand(T, N, self.zdims[k]) if k in shared else None), "diag"
+    return gather(ZZ, lambda k: self._dev(entry[k]).reshape(T, N, self.zdims[k] ** 2) if k in entry else
+                  embed(self._dev(var[k]), self.zdims[k]) if k in var else
+                  self._dev(shared[k]).expand(T, N, self.zdims[k] ** 2) if k in shared else None), True
 
   def _run_logs_stepwise(self, kd, dts, zs, Rd, fl, tx, tP, symmetrise=True, per_entry=False):
     """run_logs() for a library without the fused kernel, and run_logs(exact=True): the same per-filter schedule, step by step.

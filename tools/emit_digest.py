@@ -20,7 +20,8 @@ FALLBACK_MODELS = {"force_wide": ("kinematic6", "attitude"), "no_run_blk": ("kin
                    "no_model_defaults": ("live", "feature36"), "no_run2": ("live",), "no_tri": ("live",), "no_rts4": ("live",), "rts_one_wave": ("live",),
                    "no_rts": ("live",), "no_run": ("rand40", "feature36"),
                    "no_run_pf": ("kinematic6", "kinematic9", "live", "rand17"),
-                   "no_run_pf_r": ("kinematic6", "kinematic9", "live")}      # models on which the fallback changes the text
+                   "no_run_pf_r": ("kinematic6", "kinematic9", "live"),
+                   "no_run_pf_rd": ("kinematic6", "kinematic9", "live", "randz10")}      # models on which the fallback changes the text
 GV_MODELS = ("gv_runtime", "gv_runtime10", "gv_extra")
 LANE_GROUP_KNOBS = {      # of the lane-group family: the branches of its step kernels, the fused runs and the smoother that no default model takes
   "live": ("wide_timeline=1", "wide_lean_q=0", "wide_inline=0", "wide_db=1,wide_ft=16", "wide_lean=0,wide_lb=0,wide_db=-1,wide_ft=0", "run2_prio=3",
