@@ -23,7 +23,7 @@ fallbacks in progress and import it where they do (the one cycle among the emitt
 import types
 
 from rednose_amd.codegen import emit_common, emit_rts4, emit_run2, emit_small, emit_wide2, emit_wide3, tuning
-from rednose_amd.codegen.emit_common import routine_device_function
+from rednose_amd.codegen.emit_common import routine_device_function, NOISE_MODES, TABLE, ENTRY, DIAG
 from rednose_amd.codegen.lower import NULLSPACE_RESIDUAL, SINCOS_FAST
 
 SMALL_MAX_E = 7    # lane-per-filter register budget: x, P and the update's temporaries in VGPRs/AGPRs without spilling.  At 8
@@ -52,8 +52,8 @@ SMALL_MAX_E = 7    # lane-per-filter register budget: x, P and the update's temp
 #                      library without it ({name}_has_batch_run_pf_r() == 0, batch_run_pf_r returns ERR_UNSUPPORTED); k_run_pf and everything else stay
 #   no_run_pf_rd       the same run with a DIAGONAL noise per entry (k_run_dpf / k_run_dpf_tr) touches scratch memory or spills -> library without it
 #                      ({name}_has_batch_run_pf_rd() == 0, batch_run_pf_rd returns ERR_UNSUPPORTED); k_run_pf, k_run_rpf and everything else stay
-FALLBACKS = ("force_wide", "no_model_defaults", "no_rts4", "rts_one_wave", "no_rts", "no_run2", "no_run", "no_run_blk", "no_tri", "no_kinds", "no_run_pf",
-             "no_run_pf_r", "no_run_pf_rd")
+FALLBACKS = ("force_wide", "no_model_defaults", "no_rts4", "rts_one_wave", "no_rts", "no_run2", "no_run", "no_run_blk", "no_tri", "no_kinds") + tuple(
+  m.fallback for m in NOISE_MODES)
 KINDS_MAX = 16      # kinds of a model with a mixed-kind step: the Z table rn::k_timeline_push takes by value
 _active = frozenset()      # fallbacks of the emit() call in progress
 
@@ -76,28 +76,31 @@ def step_kinds(spec, fallbacks=None):
   return all(k.ea_sym is None and k.He_sym is None and k.zdim < emit_wide2.WIDE_Z_LDS and k.kind > 0 for k in spec.kinds)
 
 
-def run_pf(spec, fallbacks=None):
-  """Does this library get the fused run with a schedule per filter (k_run_pf: emit_small.run_pf_kernel, emit_wide3.run_pf_kernel)?  Models with a
-  fused run whose kinds take no extra arguments, MSCKF models excepted.  (Lane-group models whose batch_run is emit_run2's k_run2 get emit_wide3's
-  single-wavefront kernel, with the functions it needs emitted beside emit_run2's.)"""
+def has_run_pf(spec, noise, fallbacks=None):
+  """Does this library get the fused run with a schedule per filter in this noise flavour (emit_common.NoiseMode; the kernels are
+  emit_small.run_pf_kernel's and emit_wide3.run_pf_kernel's)?  Models with a fused run whose kinds take no extra arguments, MSCKF models excepted; the
+  per-entry flavours at most where the table's k_run_pf is, and not tied to one another: a row of k_run_dpf is zmax doubles where k_run_rpf's is
+  zmax^2.  (Lane-group models whose batch_run is emit_run2's k_run2 get emit_wide3's single-wavefront kernel, with the functions it needs emitted
+  beside emit_run2's.)"""
   fb = _active if fallbacks is None else fallbacks
-  if "no_run_pf" in fb or "no_run" in fb or spec.N > 0 or spec.dim_err > 64:
+  if noise.fallback in fb or "no_run_pf" in fb or "no_run" in fb or spec.N > 0 or spec.dim_err > 64:
     return False
   return all(k.ea_sym is None and k.He_sym is None and k.kind > 0 for k in spec.kinds)
 
 
+def run_pf(spec, fallbacks=None):
+  """has_run_pf() of the run with one R per kind (k_run_pf)."""
+  return has_run_pf(spec, TABLE, fallbacks)
+
+
 def run_pf_r(spec, fallbacks=None):
-  """Does this library get the fused run with a schedule per filter AND a noise matrix per entry (k_run_rpf: emit_small.run_rpf_kernel,
-  emit_wide3.run_rpf_kernel)?  At most where run_pf() is."""
-  fb = _active if fallbacks is None else fallbacks
-  return "no_run_pf_r" not in fb and run_pf(spec, fb)
+  """has_run_pf() of the run with a noise matrix per entry (k_run_rpf)."""
+  return has_run_pf(spec, ENTRY, fallbacks)
 
 
 def run_pf_rd(spec, fallbacks=None):
-  """Does this library get the fused run with a schedule per filter and a DIAGONAL noise per entry (k_run_dpf: emit_small.run_pf_kernel,
-  emit_wide3.run_pf_kernel with r_diag)?  At most where run_pf() is; not tied to run_pf_r(): a row is zmax doubles where k_run_rpf's is zmax^2."""
-  fb = _active if fallbacks is None else fallbacks
-  return "no_run_pf_rd" not in fb and run_pf(spec, fb)
+  """has_run_pf() of the run with a DIAGONAL noise per entry (k_run_dpf)."""
+  return has_run_pf(spec, DIAG, fallbacks)
 
 
 def _align2(n):
@@ -211,13 +214,11 @@ def _select(spec):
               (use_rts4; emit_rts4: 8 .. 22 error states) or rn::k_rts_group (MSCKF models -- their main block is smoothed, ekf_sym.py:675-686 --,
               larger models, and the fallback of k_rts4)
     use_tri   packed-triangle trace: both structures or neither (batch_run_tri writes what batch_rts_tri reads)
-    has_kinds the mixed-kind step kernel k_kinds;  has_run_pf: the fused run with a schedule per filter (k_run_pf);  has_run_pf_r: the same with a
-              noise matrix per entry (k_run_rpf);  has_run_pf_rd: with a diagonal noise per entry (k_run_dpf)"""
+    has_kinds the mixed-kind step kernel k_kinds  (the fused runs with a schedule per filter: has_run_pf(spec, noise), asked where they are emitted)"""
   if spec.dim_err > 64:
     raise NotImplementedError(f"{spec.dim_err} error states: the lane-group kernels hold one row of P per lane of a wavefront (<= 64)")
   tune = tuning.current()
-  s = types.SimpleNamespace(fam=family(spec), has_run="no_run" not in _active, has_kinds=step_kinds(spec), has_run_pf=run_pf(spec), has_run_pf_r=run_pf_r(spec),
-                            has_run_pf_rd=run_pf_rd(spec))
+  s = types.SimpleNamespace(fam=family(spec), has_run="no_run" not in _active, has_kinds=step_kinds(spec))
   wide = s.fam == "wide"
   s.step = emit_wide2 if wide else emit_small
   s.use_run2 = wide and s.has_run and tune.run2 and "no_run2" not in _active and emit_run2.applicable(spec)
@@ -518,23 +519,15 @@ def _abi_batched(spec, s):
     launch = emit_small.launch_run(spec) if s.fam == "small" else (emit_run2.launch_run() if s.use_run2 else emit_wide3.launch_run())
   a.fn("int", "batch_run", RUN_PARAMS, _run_body(launch, hip_check=s.has_run))
   # The fused run with a schedule per filter (k_run_pf): kinds (T, n), dts (T, n), R the per-kind table of batch_predict_update_kinds.  The
-  # symbols exist in every library; without the kernel batch_run_pf returns ERR_UNSUPPORTED.
-  a.fn("int", "has_batch_run_pf", "void", f"return {int(s.has_run_pf)};")
-  a.fn("int", "batch_run_pf", RUN_PF_PARAMS, _run_body(emit_small.launch_run_pf() if s.fam == "small" else emit_wide3.launch_run_pf()) if s.has_run_pf else _unsupported(
-    "batch_run_pf: not generated for this model (MSCKF model, a kind with extra arguments, no fused run, or the kernel "
-    "did not fit the register file)"))
-  # The same run with a noise matrix per entry (k_run_rpf): R (T, n, zmax^2), row (t, i) the `r_per_filter != 0` row of filter i in step t.
-  a.fn("int", "has_batch_run_pf_r", "void", f"return {int(s.has_run_pf_r)};")
-  a.fn("int", "batch_run_pf_r", RUN_PF_PARAMS, _run_body(emit_small.launch_run_rpf() if s.fam == "small" else emit_wide3.launch_run_rpf(),
-                                                         r_per_entry=True) if s.has_run_pf_r else _unsupported(
-    "batch_run_pf_r: not generated for this model (MSCKF model, a kind with extra arguments, no fused run, or the kernel "
-    "did not fit the register file)"))
-  # The same run with a diagonal noise per entry (k_run_dpf): R (T, n, zmax), the leading Z doubles of row (t, i) the variances of filter i's entry t.
-  a.fn("int", "has_batch_run_pf_rd", "void", f"return {int(s.has_run_pf_rd)};")
-  a.fn("int", "batch_run_pf_rd", RUN_PF_PARAMS, _run_body(emit_small.launch_run_dpf() if s.fam == "small" else emit_wide3.launch_run_dpf(),
-                                                          r_per_entry=True) if s.has_run_pf_rd else _unsupported(
-    "batch_run_pf_rd: not generated for this model (MSCKF model, a kind with extra arguments, no fused run, or the kernel "
-    "did not fit the register file)"))
+  # symbols exist in every library; without the kernel batch_run_pf returns ERR_UNSUPPORTED.  The same run with a noise matrix per entry
+  # (batch_run_pf_r, k_run_rpf): R (T, n, zmax^2), row (t, i) the `r_per_filter != 0` row of filter i in step t; with a diagonal noise per entry
+  # (batch_run_pf_rd, k_run_dpf): R (T, n, zmax), the leading Z doubles of row (t, i) the variances of filter i's entry t.
+  for noise in NOISE_MODES:
+    has, sym = has_run_pf(spec, noise), f"batch_run_pf{noise.sfx}"
+    a.fn("int", f"has_{sym}", "void", f"return {int(has)};")
+    launch = (emit_small if s.fam == "small" else emit_wide3).launch_run_pf(noise)
+    a.fn("int", sym, RUN_PF_PARAMS, _run_body(launch, r_per_entry=noise.per_entry) if has else _unsupported(
+      f"{sym}: not generated for this model (MSCKF model, a kind with extra arguments, no fused run, or the kernel did not fit the register file)"))
   return a
 
 

@@ -1,6 +1,8 @@
 """Pieces shared by the kernel emitters: structured (sparse-at-generation-time) matrices, the per-filter scalar slot of the lane-group
 family (SlotLayout), the per-routine device functions of the reference's scalar C ABI, and the launch text of the step-granular
-kernels (launch_*)."""
+kernels (launch_*), and the noise flavours of the fused run with a schedule per filter (NoiseMode)."""
+from typing import NamedTuple
+
 import sympy as sp
 
 from rednose_amd.codegen.lower import Block, vector_names
@@ -93,6 +95,46 @@ class SlotLayout:
     self.OFF_RP = self.OFF_RF + (EADIM * self.zf + EADIM if self.zf else 0)
     self.OFF_YP = self.OFF_RP + (zp ** 2 if self.zf else 0)
     return self.OFF_YP + (zp if self.zf else 0)
+
+
+class NoiseMode(NamedTuple):
+  """One flavour of the observation noise in the fused run with a schedule per filter: what the kernel emitters, emit's C ABI, gen_code's
+  fallbacks and BatchedEKF.run_logs select on.  Where the flavours' wording differs irregularly the record carries the text as it is."""
+  sfx: str               # C ABI: {name}_batch_run_pf{sfx} and {name}_has_batch_run_pf{sfx}
+  kernel: str            # kernel stem ({kernel}_tr: the lane-per-filter family's kernel with the filtered trace)
+  update: str            # update_{kind}_rows{update}: the lane-group family's predicated updates
+  fallback: str          # of emit.FALLBACKS: the library without this kernel
+  per_entry: bool        # gR is (T, n, row(zmax)), the lane's (group's) own rows staged in registers; False: one row per kind, a table in LDS
+  diag: bool             # a row holds the entry's variances
+  what: str              # the flavour in gen_code's log sentence, after "a schedule per filter"
+  title_small: str       # emit_small.run_pf_kernel's title: untraced (K, ZZ) ...
+  title_small_tr: str    # ... and with the filtered trace (K)
+  title_wide: str        # emit_wide3.run_pf_kernel's title (zmax, ZZ)
+
+  def row(self, zmax):
+    """Doubles per row of gR."""
+    return zmax if self.diag else zmax * zmax
+
+
+TABLE = NoiseMode(
+  sfx="", kernel="k_run_pf", update="_pf", fallback="no_run_pf", per_entry=False, diag=False, what="",
+  title_small="// ---- fused run, a schedule per filter (kinds (T, n), dts (T, n)): blocks of {K} steps in registers (emit_small.run_pf_kernel) ----",
+  title_small_tr="// ---- fused run, a schedule per filter, with the filtered trace: blocks of {K} steps (see emit_small.run_pf_kernel) ----------------",
+  title_wide="""// ---- fused multi-step run, a schedule per filter: kinds (T, n), dts (T, n); z is (T, n, {zmax}) in: z, out: y; gR one row per kind -----------
+// k_run's phases per step; a group takes part in those its own entry asks for (see emit_wide3.run_pf_kernel).""")
+ENTRY = NoiseMode(
+  sfx="_r", kernel="k_run_rpf", update="_rpf", fallback="no_run_pf_r", per_entry=True, diag=False, what=" and R per entry",
+  title_small="// ---- fused run, a schedule per filter, R per entry (gR (T, n, {ZZ})): blocks of {K} steps in registers (emit_small.run_pf_kernel) ----",
+  title_small_tr="// ---- fused run, a schedule per filter and R per entry, with the filtered trace: blocks of {K} steps (see emit_small.run_pf_kernel) ----",
+  title_wide="""// ---- fused multi-step run, a schedule per filter and R per entry: kinds (T, n), dts (T, n); z is (T, n, {zmax}) in: z, out: y; gR (T, n, {ZZ}) -----------
+// k_run_pf with the group's own row of R, a step ahead in registers (see emit_wide3.run_pf_kernel).""")
+DIAG = NoiseMode(
+  sfx="_rd", kernel="k_run_dpf", update="_dpf", fallback="no_run_pf_rd", per_entry=True, diag=True, what=" and a diagonal R per entry",
+  title_small="// ---- fused run, a schedule per filter, diagonal R per entry (gR (T, n, {ZZ})): blocks of {K} steps in registers (emit_small.run_pf_kernel) ----",
+  title_small_tr="// ---- fused run, a schedule per filter and a diagonal R per entry, with the filtered trace: blocks of {K} steps (see emit_small.run_pf_kernel) ----",
+  title_wide="""// ---- fused multi-step run, a schedule per filter and a diagonal R per entry: kinds (T, n), dts (T, n); z is (T, n, {zmax}) in: z, out: y; gR (T, n, {ZZ}) -----------
+// k_run_rpf with the group's own row of variances, a step ahead in registers (see emit_wide3.run_pf_kernel).""")
+NOISE_MODES = (TABLE, ENTRY, DIAG)      # in the order of emission
 
 
 def ea_count(k):

@@ -35,7 +35,7 @@ import sympy as sp
 
 from rednose_amd.codegen import emit_common, tuning
 from rednose_amd.codegen.lower import Block, vector_names
-from rednose_amd.codegen.emit_common import SMat, term, sum_terms, innovation_solver, ea_count
+from rednose_amd.codegen.emit_common import SMat, term, sum_terms, innovation_solver, ea_count, NOISE_MODES, TABLE, ENTRY, DIAG
 from rednose_amd.codegen.emit_common import ind as _ind
 
 TILES = "(n + 63) >> 6"      # tiles of a launch: 64 filters per wavefront
@@ -464,15 +464,9 @@ __global__ __launch_bounds__(64) void k_predict(double* __restrict__ gx, double*
     out.append(run_kernel_blk(spec, norm, trace=True))
   else:                            # fallback "no_run_blk" (the blocked kernels spilled): the step-at-a-time k_run serves both
     out.append(run_kernel(spec, norm))
-  if emit.run_pf(spec):            # the fused run with a schedule per filter: k_run_pf (no trace) and k_run_pf_tr (filtered trace)
-    out.append(run_pf_kernel(spec, norm))
-    out.append(run_pf_kernel(spec, norm, trace=True))
-  if emit.run_pf_r(spec):          # the same with a noise matrix per entry: k_run_rpf and k_run_rpf_tr
-    out.append(run_pf_kernel(spec, norm, r_entry=True))
-    out.append(run_pf_kernel(spec, norm, trace=True, r_entry=True))
-  if emit.run_pf_rd(spec):         # the same with a diagonal noise per entry: k_run_dpf and k_run_dpf_tr
-    out.append(run_pf_kernel(spec, norm, r_diag=True))
-    out.append(run_pf_kernel(spec, norm, trace=True, r_diag=True))
+  # the fused run with a schedule per filter, R per kind, per entry, its variances per entry: k_run_pf, k_run_rpf, k_run_dpf (no trace) and
+  # their `_tr` (filtered trace)
+  out += [run_pf_kernel(spec, norm, trace, noise) for noise in NOISE_MODES if emit.has_run_pf(spec, noise) for trace in (False, True)]
   return "\n".join(out)
 
 
@@ -1154,7 +1148,7 @@ def run_pf_rd_block(spec):
   return K
 
 
-def run_pf_kernel(spec, norm, trace=False, r_entry=False, r_diag=False):
+def run_pf_kernel(spec, norm, trace=False, noise=TABLE):
   """The fused run with a SCHEDULE PER FILTER (kinds (T, n), dts (T, n)): N independent logs replayed in one launch.  run_kernel_blk's
   structure -- blocks of K steps in registers, ONE vmcnt(0) per block, y and the flags of block b stored at the start of block b + 1 --
   with the schedule per lane: the lane of filter i loads its own kinds[t * n + i] and dts[t * n + i] of the next block's K steps with that
@@ -1166,41 +1160,26 @@ def run_pf_kernel(spec, norm, trace=False, r_entry=False, r_diag=False):
   trace=True: k_run_pf_tr, every step's pair of every filter (stepped or not: the trace is dense) leaves through the LDS image as in
   k_run_blk_tr; the image of the final write-back is loaded again in front of it, since the trace has overwritten the one that came in.
 
-  r_entry=True: k_run_rpf / k_run_rpf_tr, a NOISE MATRIX PER ENTRY: gR is (T, n, zmax^2) and row (t, i) is the R of filter i's entry t (the `r_per_filter`
+  noise=ENTRY: k_run_rpf / k_run_rpf_tr, a NOISE MATRIX PER ENTRY: gR is (T, n, zmax^2) and row (t, i) is the R of filter i's entry t (the `r_per_filter`
   row of k_kinds).  No table in LDS: the lane of filter i stages its own rows of the next block in registers, loaded with that block's observation
   rows and schedule under the same single wait (zmax^2 doubles per step and buffer, hence the shorter block run_pf_r_block), clamped like them at
   rows past T and lanes past cnt.  A lane copies the leading Z^2 doubles of a row inside the case of its own kind, which an idle or flag-8 lane never
   enters: whatever such a row and the tail of the others hold (NaN included) stays in staging registers nothing reads.
 
-  r_diag=True: k_run_dpf / k_run_dpf_tr, a DIAGONAL NOISE PER ENTRY: k_run_rpf's structure with rows of zmax doubles -- gR is (T, n, zmax), the leading Z
+  noise=DIAG: k_run_dpf / k_run_dpf_tr, a DIAGONAL NOISE PER ENTRY: k_run_rpf's structure with rows of zmax doubles -- gR is (T, n, zmax), the leading Z
   doubles of row (t, i) the variances of filter i's entry t.  Staged, clamped and waited for exactly like k_run_rpf's rows (a third of the registers
   at zmax = 3; the block is run_pf_rd_block's).  Inside the case of its own kind a lane fills the update's
   Rk[Z * Z] with its Z variances on the diagonal and literal zeros elsewhere; the update's statements are those of the other two kernels.
 
   The kernel's text is _blocked_run's; what is here is the schedule per lane, a register per step of the block, the table of R and `stepped`."""
-  assert not (r_entry and r_diag)
   zmax = max(k.zdim for k in spec.kinds)
-  ZZ = zmax ** 2
+  ZZ = noise.row(zmax)      # doubles per row of gR
   NK = len(spec.kinds)
-  K = run_pf_r_block(spec) if r_entry else run_pf_rd_block(spec) if r_diag else run_pf_block(spec)
-  if r_diag:      # Rk of a kind: its Z variances on the diagonal (i a constant of the unrolled loop)
-    r_expr = lambda idx: f"(i % {spec.kinds[idx].zdim + 1} == 0) ? Rc[u][i / {spec.kinds[idx].zdim + 1}] : 0.0"
-  else:
-    r_expr = "Rc[u][i]" if r_entry else (lambda idx: f"s_R[{idx * ZZ} + i]")
-  cases = kind_cases(spec, "_regs_sym", "cur[u]", r_expr, ind=12)
-  known = " ".join(f"case {k.kind}:" for k in spec.kinds)
-  if r_entry or r_diag:
-    if r_diag:
-      ZZ = zmax      # doubles per row of gR
-      names = dict(kname="k_run_dpf_tr" if trace else "k_run_dpf", title=(
-        f"// ---- fused run, a schedule per filter and a diagonal R per entry, with the filtered trace: blocks of {K} steps (see emit_small.run_pf_kernel) ----"
-        if trace else
-        f"// ---- fused run, a schedule per filter, diagonal R per entry (gR (T, n, {ZZ})): blocks of {K} steps in registers (emit_small.run_pf_kernel) ----"))
-    else:
-      names = dict(kname="k_run_rpf_tr" if trace else "k_run_rpf", title=(
-        f"// ---- fused run, a schedule per filter and R per entry, with the filtered trace: blocks of {K} steps (see emit_small.run_pf_kernel) ----"
-        if trace else
-        f"// ---- fused run, a schedule per filter, R per entry (gR (T, n, {ZZ})): blocks of {K} steps in registers (emit_small.run_pf_kernel) ----"))
+  K = {TABLE: run_pf_block, ENTRY: run_pf_r_block, DIAG: run_pf_rd_block}[noise](spec)
+  names = dict(kname=noise.kernel + ("_tr" if trace else ""), title=(noise.title_small_tr if trace else noise.title_small).format(K=K, ZZ=ZZ))
+  if noise.per_entry:
+    # Rk of a kind: the lane's staged row, or its Z variances on the diagonal (i a constant of the unrolled loop)
+    r_expr = (lambda idx: f"(i % {spec.kinds[idx].zdim + 1} == 0) ? Rc[u][i / {spec.kinds[idx].zdim + 1}] : 0.0") if noise.diag else "Rc[u][i]"
     # the rows of R travel like the schedule: the lane's own row of every step of the block, addressed by pointer increments
     table = dict(sched_ptrs=f"\n    const double* rrow = gR + (base + lc) * {ZZ};", decl_d=f", Rc[{K}][{ZZ}], Rn[{K}][{ZZ}]",
                  issue_ptrs=f"\n      const double* rp_ = rrow + tb0_ * (n * {ZZ});",
@@ -1209,15 +1188,14 @@ def run_pf_kernel(spec, norm, trace=False, r_entry=False, r_diag=False):
                  pin_row=f"\n#pragma unroll\n        for (int i = 0; i < {ZZ}; i++) rn::pin(Rn[u][i]);",
                  rot_row=f"\n#pragma unroll\n        for (int i = 0; i < {ZZ}; i++) Rc[u][i] = Rn[u][i];")
   else:
-    names = dict(kname="k_run_pf_tr" if trace else "k_run_pf", title=(
-      f"// ---- fused run, a schedule per filter, with the filtered trace: blocks of {K} steps (see emit_small.run_pf_kernel) ----------------"
-      if trace else
-      f"// ---- fused run, a schedule per filter (kinds (T, n), dts (T, n)): blocks of {K} steps in registers (emit_small.run_pf_kernel) ----"),
-      lds=dict(R=NK * ZZ), fill=f"\n  for (int i = lane; i < {NK * ZZ}; i += 64) s_R[i] = gR[i];      // one row per kind, in the order of the model's kinds")
+    r_expr = lambda idx: f"s_R[{idx * ZZ} + i]"      # noqa: E731
+    names.update(lds=dict(R=NK * ZZ), fill=f"\n  for (int i = lane; i < {NK * ZZ}; i += 64) s_R[i] = gR[i];      // one row per kind, in the order of the model's kinds")
     table = dict.fromkeys(("sched_ptrs", "decl_d", "issue_ptrs", "issue_row", "issue_step", "pin_row", "rot_row"), "")
+  cases = kind_cases(spec, "_regs_sym", "cur[u]", r_expr, ind=12)
+  known = " ".join(f"case {k.kind}:" for k in spec.kinds)
   return _blocked_run(
     spec, norm, trace, K, **names,
-    helpers="" if trace or r_entry or r_diag else """
+    helpers="" if trace or noise.per_entry else """
 __device__ __forceinline__ void pin_k(int& v) { asm volatile("" : "+v"(v)); }
 """,
     ragged_note="// lanes past the end of a ragged tile follow a copy of the last filter's schedule and rows and store nothing",
@@ -1268,16 +1246,8 @@ def _launch_blocked(kname, more=""):
   }}"""
 
 
-def launch_run_pf():
-  return _launch_blocked("k_run_pf")
-
-
-def launch_run_rpf():
-  return _launch_blocked("k_run_rpf")
-
-
-def launch_run_dpf():
-  return _launch_blocked("k_run_dpf")
+def launch_run_pf(noise=TABLE):
+  return _launch_blocked(noise.kernel)
 
 
 def launch_run(spec=None):

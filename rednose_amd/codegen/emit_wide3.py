@@ -31,7 +31,7 @@ emit_wide2 -- one wavefront per SIMD cannot overlap its own HBM round trip; numb
 import types
 
 from rednose_amd.codegen import emit_wide2 as w2, tuning
-from rednose_amd.codegen.emit_common import EADIM, SlotLayout, ea_count, ind, term, sum_terms
+from rednose_amd.codegen.emit_common import EADIM, SlotLayout, ea_count, ind, term, sum_terms, NOISE_MODES, TABLE
 
 
 def ea_max(spec):
@@ -178,7 +178,7 @@ def predict_fn(spec, qdiag=False, pf=False):
   return "\n".join([head] + ind(b) + ["}"])
 
 
-def update_fn(spec, k, pf=False, r_entry=False, r_diag=False):
+def update_fn(spec, k, pf=False, noise=TABLE):
   """Matrix part of the update of kind k on register rows.  y, the non-trivial entries of He = H H_mod and, for feature-track
   kinds, the Householder reflectors and the projected noise are read from the filter's slot (phase 1 put them there); dx and
   the gate / rank flags go back to it.
@@ -188,14 +188,14 @@ def update_fn(spec, k, pf=False, r_entry=False, r_diag=False):
   takes zero coefficients into both rank-Z passes (row -+= 0 * 0: the rows come out unchanged, whatever stale numbers its slot holds), and
   writes nothing into its slot.
 
-  r_entry=True (with pf) emits `update_{kind}_rows_rpf` for k_run_rpf, whose R is per entry: the same statements, except that `gR` is the group's OWN
+  noise=ENTRY (with pf) emits `update_{kind}_rows_rpf` for k_run_rpf, whose R is per entry: the same statements, except that `gR` is the group's OWN
   row and its Z * Z doubles are taken only where `mine` -- the row of a group that is idle, flagged 8 or of another kind may hold anything, NaN
   included, and such a group factors the identity instead (its coefficients are zeroed either way, but 0 * NaN is NaN).
 
-  r_diag=True (with pf) emits `update_{kind}_rows_dpf` for k_run_dpf, whose R is the group's own row of Z variances, taken only where `mine` (ones
+  noise=DIAG (with pf) emits `update_{kind}_rows_dpf` for k_run_dpf, whose R is the group's own row of Z variances, taken only where `mine` (ones
   otherwise: the identity as above).  The noise stays a vector through the update -- S = HPH with S[i][i] += r[i], the gate's 1e16 on the Z
   variances, the Joseph term K R as kk[zi] * r[zi] -- so Z doubles live where the other flavours hold Z * Z."""
-  assert not (pf and k.He_sym is not None) and (pf or not (r_entry or r_diag)) and not (r_entry and r_diag)
+  assert not (pf and k.He_sym is not None) and (pf or noise is TABLE)
   E, Zf = spec.dim_err, k.zdim
   _, R, _ = layout(spec)
   lay, _, Hss, _ = w2.slot_tables(spec, RunLayout)
@@ -203,15 +203,15 @@ def update_fn(spec, k, pf=False, r_entry=False, r_diag=False):
   feat = k.He_sym is not None
   Z = Zf - EADIM if feat else Zf
   RF, RB = lay.OFF_RF, lay.OFF_RF + EADIM * Zf
-  b = ["(void)sP;", f"double R[{Z if r_diag else Z * Z}];"]
+  b = ["(void)sP;", f"double R[{Z if noise.diag else Z * Z}];"]
   if feat:
     b += ["#pragma unroll", f"for (int i = 0; i < {Z * Z}; i++) R[i] = sl[{lay.OFF_RP} + i];      // A^T R A (phase 1)", "(void)gR;",
           f"const double rank_deficient = sl[{lay.OFF_FL}];      // 4.0 when phase 1 found Hea rank deficient"]
-  elif r_entry:
+  elif noise.diag:
+    b += ["#pragma unroll", f"for (int i = 0; i < {Z}; i++) R[i] = mine ? gR[i] : 1.0;      // the variances of the group's entry"]
+  elif noise.per_entry:
     b += ["#pragma unroll", f"for (int i = 0; i < {Z * Z}; i++) R[i] = (i % {Z + 1} == 0) ? 1.0 : 0.0;",
           "if (mine) {", "#pragma unroll", f"  for (int i = 0; i < {Z * Z}; i++) R[i] = gR[i];", "}"]
-  elif r_diag:
-    b += ["#pragma unroll", f"for (int i = 0; i < {Z}; i++) R[i] = mine ? gR[i] : 1.0;      // the variances of the group's entry"]
   else:
     b += ["#pragma unroll", f"for (int i = 0; i < {Z * Z}; i++) R[i] = gR[i];"]
   # G = He P: G[z][j] = sum_k He[z][k] P[k][j]; with P = P^T (up to the Joseph form's rounding) that is row j of P against
@@ -229,8 +229,8 @@ def update_fn(spec, k, pf=False, r_entry=False, r_diag=False):
     b.append(f"if (ok{s}) {{ " + " ".join(f"sG[{zi} * {E} + rr{s}] = kk{s}[{zi}];" for zi in range(Z)) + " }")
   b.append("rn::wave_lds_sync();")
   b += _tl(10)
-  b.append(f"double HPH[{Z * Z}], Rl[{Z if r_diag else Z * Z}], S[{Z * Z}], L[{Z * Z}], iL[{Z}];")
-  if r_diag:      # S = HPH + diag(Rl), `scale` in front of the variances
+  b.append(f"double HPH[{Z * Z}], Rl[{Z if noise.diag else Z * Z}], S[{Z * Z}], L[{Z * Z}], iL[{Z}];")
+  if noise.diag:      # S = HPH + diag(Rl), `scale` in front of the variances
     s_of = lambda scale: ["#pragma unroll", f"for (int i = 0; i < {Z * Z}; i++) S[i] = HPH[i];",      # noqa: E731
                           "#pragma unroll", f"for (int i = 0; i < {Z}; i++) {{ Rl[i] = {scale}[i]; S[i * {Z + 1}] += Rl[i]; }}"]
   if feat:
@@ -243,12 +243,12 @@ def update_fn(spec, k, pf=False, r_entry=False, r_diag=False):
     for zi in range(Z):
       for w in range(Z):
         b.append(f"HPH[{zi * Z + w}] = {sum_terms(term(cf, f'sG[{zi} * {E} + {j}]') for j, cf in Hs.row_nz(w))};")
-  b += (s_of("R") if r_diag else ["#pragma unroll", f"for (int i = 0; i < {Z * Z}; i++) {{ Rl[i] = R[i]; S[i] = HPH[i] + Rl[i]; }}"]) + [
+  b += (s_of("R") if noise.diag else ["#pragma unroll", f"for (int i = 0; i < {Z * Z}; i++) {{ Rl[i] = R[i]; S[i] = HPH[i] + Rl[i]; }}"]) + [
         f"rn::spd_factor<{Z}>(S, L, iL);", "int gated = 0;"]
   if k.maha_test:
     b += ["{", f"  double v[{Z}] = {{{', '.join(f'sl[{(lay.OFF_YP if feat else lay.OFF_Y) + i}]' for i in range(Z))}}};", f"  rn::spd_forward<{Z}>(L, iL, v);",
           "  const double d2 = " + " + ".join(f"v[{i}]*v[{i}]*iL[{i}]" for i in range(Z)) + ";", f"  if (d2 > {k.maha_thresh!r}) {{", "    gated = 1;"] + (
-          ["    " + l_ if not l_.startswith("#") else l_ for l_ in s_of("1.0e16 * Rl")] if r_diag else
+          ["    " + l_ if not l_.startswith("#") else l_ for l_ in s_of("1.0e16 * Rl")] if noise.diag else
           ["#pragma unroll", f"    for (int i = 0; i < {Z * Z}; i++) {{ Rl[i] = 1.0e16 * Rl[i]; S[i] = HPH[i] + Rl[i]; }}"]) + [
           f"    rn::spd_factor<{Z}>(S, L, iL);", "  }", "}"]
   b += _tl(11)
@@ -270,7 +270,7 @@ def update_fn(spec, k, pf=False, r_entry=False, r_diag=False):
     b.append(f"double Dm{s}[{Z}];")
     for zi in range(Z):
       c = f"Cf{s}[{EADIM + zi}]" if feat else sum_terms(term(cf, f"row{s}[{j}]") for j, cf in Hs.row_nz(zi))
-      kr = f"kk{s}[{zi}]*Rl[{zi}]" if r_diag else " + ".join(f"kk{s}[{w}]*Rl[{w * Z + zi}]" for w in range(Z))
+      kr = f"kk{s}[{zi}]*Rl[{zi}]" if noise.diag else " + ".join(f"kk{s}[{w}]*Rl[{w * Z + zi}]" for w in range(Z))
       b.append(f"Dm{s}[{zi}] = " + ("rank_deficient != 0.0 ? 0.0 : " if feat else "") + ("!mine ? 0.0 : " if pf else "") + f"({kr}) - ({c});")
   b.append("rn::wave_lds_sync();      // every lane has taken G (and y): the buffer takes K^T, the slot takes dx and the flags")
   fl = "(double)gated + rank_deficient" if feat else "(double)gated"
@@ -286,7 +286,7 @@ def update_fn(spec, k, pf=False, r_entry=False, r_diag=False):
   b.append("rn::wave_lds_sync();      // the broadcast buffer is free again")
   rows = ", ".join(f"double (&row{s})[{E}]" for s in range(R))
   idx = ", ".join(f"const int rr{s}, const int rc{s}, const bool ok{s}" for s in range(R))
-  head = (f"__device__ __forceinline__ void update_{k.kind}_rows{('_dpf' if r_diag else '_rpf' if r_entry else '_pf') if pf else ''}({rows}, const double* __restrict__ gR, double* sP, "
+  head = (f"__device__ __forceinline__ void update_{k.kind}_rows{noise.update if pf else ''}({rows}, const double* __restrict__ gR, double* sP, "
           f"double* sG, const double* sl, double* sw, {idx}{', const bool mine' if pf else ''}{_tl_arg()}) {{")
   return "\n".join([head] + ind(b) + ["}"])
 
@@ -301,14 +301,12 @@ def kernels(spec, with_run=True):
   slot_note = "fused run: doubles per scalar slot" if with_run else "doubles per scalar slot of the single-wavefront layout"
   consts = [f"constexpr int GLR = {GL};    // fused run: lanes per filter", f"constexpr int RPL = {R};    // rows of P per lane",
             f"constexpr int FPWR = {FPW};   // filters per wavefront", f"constexpr int SLOT_R = {lay.SLOT};   // {slot_note}", ""]
-  # the fused run with a schedule per filter: predicated matrix phases + k_run_pf
-  pf = []
-  if emit.run_pf(spec):
-    pf = [predict_fn(spec, pf=True), predict_fn(spec, qdiag=True, pf=True)] + [update_fn(spec, k, pf=True) for k in spec.kinds] + [run_pf_kernel(spec)]
-    if emit.run_pf_r(spec):      # the same with a noise matrix per entry: the updates that take R only where `mine` + k_run_rpf
-      pf += [update_fn(spec, k, pf=True, r_entry=True) for k in spec.kinds] + [run_pf_kernel(spec, r_entry=True)]
-    if emit.run_pf_rd(spec):     # the same with a diagonal noise per entry: the updates that take the Z variances only where `mine` + k_run_dpf
-      pf += [update_fn(spec, k, pf=True, r_diag=True) for k in spec.kinds] + [run_pf_kernel(spec, r_diag=True)]
+  # the fused run with a schedule per filter: the predicated predict once, then per noise flavour its predicated updates (per entry: they take
+  # R, or the Z variances, only where `mine`) + its kernel: k_run_pf, k_run_rpf, k_run_dpf
+  pf = [predict_fn(spec, pf=True), predict_fn(spec, qdiag=True, pf=True)] if emit.run_pf(spec) else []
+  for noise in NOISE_MODES:
+    if emit.has_run_pf(spec, noise):
+      pf += [update_fn(spec, k, pf=True, noise=noise) for k in spec.kinds] + [run_pf_kernel(spec, noise)]
   if not with_run:
     # the model's batch_run is emit_run2's k_run2; the fused run with a schedule per filter is this module's single-wavefront structure:
     # the scalar phases against RunLayout, the predicated matrix phases and k_run_pf follow the constants
@@ -586,7 +584,7 @@ def run_kernel(spec):
     after_step=aug)
 
 
-def run_pf_kernel(spec, r_entry=False, r_diag=False):
+def run_pf_kernel(spec, noise=TABLE):
   """k_run_pf of the lane-group family: k_run's structure (GL lanes per filter, rows of P in registers, FPW filters per wavefront) with a
   SCHEDULE PER FILTER, kinds (T, n) and dts (T, n).  Every lane of a group fetches its filter's kind and dt (one address per group), a step
   ahead like the observations.  The scalar phases run on lane c == 0 of the groups that step, each on its own kind and dt.  The matrix phases
@@ -597,40 +595,30 @@ def run_pf_kernel(spec, r_entry=False, r_diag=False):
   groups that stepped put their rows into it.  Above 32 error states a filter owns the wavefront and the tests are uniform anyway.
   (_fused_run holds the kernel's text.)
 
-  r_entry=True: k_run_rpf, a NOISE MATRIX PER ENTRY -- gR is (T, n, zmax^2), row (t, i) the R of filter i's entry t.  Every lane of a group reads its
+  noise=ENTRY: k_run_rpf, a NOISE MATRIX PER ENTRY -- gR is (T, n, zmax^2), row (t, i) the R of filter i's entry t.  Every lane of a group reads its
   filter's row (one address per group, like the schedule) a step ahead: the row of step t + 1 is requested once the update of step t has consumed
   the registers, and lands under the rest of the step with the next kind, dt and observation.  The request is unconditional on a row inside the
   buffer (group gg, the last row again at t + 1 == T); what it brings may be NaN (idle entries, entries of an unknown kind, the tail of a row), and
   `update_{kind}_rows_rpf` takes the values only where `mine`.
 
-  r_diag=True: k_run_dpf, a DIAGONAL NOISE PER ENTRY -- gR is (T, n, zmax), the leading Z doubles of row (t, i) the variances of filter i's entry t.
+  noise=DIAG: k_run_dpf, a DIAGONAL NOISE PER ENTRY -- gR is (T, n, zmax), the leading Z doubles of row (t, i) the variances of filter i's entry t.
   k_run_rpf with rows of zmax doubles, Re[zmax]: requested, waited for and predicated in the same places (`update_{kind}_rows_dpf`)."""
-  assert not (r_entry and r_diag)
   E = spec.dim_err
   _, R, _ = layout(spec)
   lay = w2.slot_tables(spec, RunLayout)[0]
   zmax = max(k.zdim for k in spec.kinds)
-  ZZ = zmax * zmax
+  ZZ = noise.row(zmax)      # doubles per row of gR
   rows, idx = _row_args(R)
-  sfx = "dpf" if r_diag else "rpf" if r_entry else "pf"
   nlc = chr(10)
   known = " ".join(f"case {k.kind}:" for k in spec.kinds)
   scal_cases = nlc.join(f"          case {k.kind}: scal_obs_{k.kind}_r(sl, sl + {lay.OFF_Y}); break;" for k in spec.kinds)
   mat = nlc.join(f"""      {{
         const bool mine = step && kind == {k.kind};
-        if (__any(mine)) update_{k.kind}_rows_{sfx}({rows}, {"Re" if r_entry or r_diag else f"gR + {i * ZZ}"}, sP, s_G + gg * {zmax * E}, sl, sl, {idx}, mine{_tl_arg(True)});
+        if (__any(mine)) update_{k.kind}_rows{noise.update}({rows}, {"Re" if noise.per_entry else f"gR + {i * ZZ}"}, sP, s_G + gg * {zmax * E}, sl, sl, {idx}, mine{_tl_arg(True)});
       }}""" for i, k in enumerate(spec.kinds))
   id0_guard = "true" if not spec.identity_at_dt0() else "dt != 0.0"
-  title = f"""// ---- fused multi-step run, a schedule per filter: kinds (T, n), dts (T, n); z is (T, n, {zmax}) in: z, out: y; gR one row per kind -----------
-// k_run's phases per step; a group takes part in those its own entry asks for (see emit_wide3.run_pf_kernel)."""
   r_first, r_next = "", ""
-  if r_entry or r_diag:
-    title = f"""// ---- fused multi-step run, a schedule per filter and R per entry: kinds (T, n), dts (T, n); z is (T, n, {zmax}) in: z, out: y; gR (T, n, {ZZ}) -----------
-// k_run_pf with the group's own row of R, a step ahead in registers (see emit_wide3.run_pf_kernel)."""
-    if r_diag:
-      ZZ = zmax      # doubles per row of gR
-      title = f"""// ---- fused multi-step run, a schedule per filter and a diagonal R per entry: kinds (T, n), dts (T, n); z is (T, n, {zmax}) in: z, out: y; gR (T, n, {ZZ}) -----------
-// k_run_rpf with the group's own row of variances, a step ahead in registers (see emit_wide3.run_pf_kernel)."""
+  if noise.per_entry:
     r_first = f"""    // the group's own row of R, a step ahead like its schedule entry; taken by the updates only where the group carries their kind
     double Re[{ZZ}];
 #pragma unroll
@@ -644,7 +632,7 @@ def run_pf_kernel(spec, r_entry=False, r_diag=False):
         for (int i = 0; i < {ZZ}; i++) Re[i] = rp_[i];
       }}"""
   return _fused_run(
-    spec, True, title=title, kname="k_run_dpf" if r_diag else "k_run_rpf" if r_entry else None,
+    spec, True, title=noise.title_wide.format(zmax=zmax, ZZ=ZZ), kname=noise.kernel,
     pre_loop="""    bool stepped = false;
     // the group's own schedule entry, a step ahead (every lane of a group reads its filter's: one address per group)
     int kind_n = kinds[base + gg];
@@ -679,16 +667,8 @@ def _launch(kname, more=""):
                      x, P, Q, kinds, dts, T, z, R, n, norm_quats, flags, trace_x, trace_P{more});"""
 
 
-def launch_run_pf():
-  return _launch("k_run_pf")
-
-
-def launch_run_rpf():
-  return _launch("k_run_rpf")
-
-
-def launch_run_dpf():
-  return _launch("k_run_dpf")
+def launch_run_pf(noise=TABLE):
+  return _launch(noise.kernel)
 
 
 def launch_run():

@@ -10,6 +10,7 @@ import numpy as np
 from rednose_amd import build as rn_build
 from rednose_amd.codegen.spec import build_spec
 from rednose_amd.codegen.emit import emit
+from rednose_amd.codegen.emit_common import NOISE_MODES, TABLE, ENTRY, DIAG
 from rednose_amd.helpers import KalmanError, load_code
 from rednose_amd.helpers.chi2_lookup import chi2_ppf
 
@@ -71,29 +72,19 @@ def gen_code(folder, name, f_sym, dt_sym, x_sym, obs_eqs, dim_x, dim_err, eskf_p
 
     usage, bad = build()
     if not os.environ.get("RN_ALLOW_SPILLS"):
-      def drop_run_pf():
-        # this kernel alone is dropped, every other structure of the model stays as it is ({name}_has_batch_run_pf() == 0): checked on the first
-        # build and again behind no_run_blk, which re-emits k_run_pf with another block size -- never left to force_wide or no_run below
-        pf_bad = [k for k in bad if k.startswith("k_run_pf")]
-        return fall_back("no_run_pf", f"the fused run with a schedule per filter {pf_bad} does not fit the register file: library without it") if pf_bad else (usage, bad)
-      def drop_run_pf_r():
-        # likewise the same run with a noise matrix per entry ({name}_has_batch_run_pf_r() == 0): this kernel alone, k_run_pf stays
-        rpf_bad = [k for k in bad if k.startswith("k_run_rpf")]
-        return fall_back("no_run_pf_r", f"the fused run with a schedule per filter and R per entry {rpf_bad} does not fit the register file: library "
-                                        "without it") if rpf_bad else (usage, bad)
-      def drop_run_pf_rd():
-        # and the one with a diagonal noise per entry ({name}_has_batch_run_pf_rd() == 0): this kernel alone, k_run_pf and k_run_rpf stay
-        dpf_bad = [k for k in bad if k.startswith("k_run_dpf")]
-        return fall_back("no_run_pf_rd", f"the fused run with a schedule per filter and a diagonal R per entry {dpf_bad} does not fit the register file: "
-                                         "library without it") if dpf_bad else (usage, bad)
-      usage, bad = drop_run_pf_rd()
-      usage, bad = drop_run_pf_r()
-      usage, bad = drop_run_pf()
+      def drop(noise):
+        # a fused run with a schedule per filter that does not fit: this kernel alone is dropped, the other noise flavours and every other structure
+        # of the model stay as they are ({name}_has_batch_run_pf{sfx}() == 0): checked on the first build and again behind no_run_blk, which re-emits
+        # these kernels with another block size -- never left to force_wide or no_run below
+        pf_bad = [k for k in bad if k.startswith(noise.kernel)]
+        return fall_back(noise.fallback, f"the fused run with a schedule per filter{noise.what} {pf_bad} does not fit the register file: library "
+                                         "without it") if pf_bad else (usage, bad)
+      for noise in reversed(NOISE_MODES):
+        usage, bad = drop(noise)
       if "k_run_blk" in bad or "k_run_blk_tr" in bad:
         usage, bad = fall_back("no_run_blk", "a blocked fused run spills registers: the step-at-a-time k_run serves fused runs instead")
-        usage, bad = drop_run_pf_rd()
-        usage, bad = drop_run_pf_r()
-        usage, bad = drop_run_pf()
+        for noise in reversed(NOISE_MODES):
+          usage, bad = drop(noise)
       if bad and rn_emit.family(spec, ()) == "small":
         usage, bad = fall_back("force_wide", f"lane-per-filter kernels {bad} spill registers: regenerating in the lane-group family")
       if "k_rts4" in bad:
@@ -1683,9 +1674,20 @@ class BatchedEKF:
       self._keepalive_step = (zt, Rt, eat)
 
   # -- N independent logs in one launch ---------------------------------------------------------------
-  def _has_batch_run_pf(self):
-    fn = getattr(self._lib, f"{self.name}_has_batch_run_pf", None)
+  def _has_sym(self, sym):
+    """{name}_has_{sym}() == 1; False for a library from before the symbol."""
+    fn = getattr(self._lib, f"{self.name}_has_{sym}", None)
     return fn is not None and int(fn()) == 1
+
+  # one per NoiseMode, looked up on the object when run_logs runs: an object may override one (a library "without" that kernel)
+  def _has_batch_run_pf(self):
+    return self._has_sym("batch_run_pf")
+
+  def _has_batch_run_pf_r(self):
+    return self._has_sym("batch_run_pf_r")
+
+  def _has_batch_run_pf_rd(self):
+    return self._has_sym("batch_run_pf_rd")
 
   def run_logs(self, ts, kinds, zs, Rs, trace=False, flags=False, out=None, exact=False):
     """Replay N recorded logs, one per filter, in ONE launch ({name}_batch_run_pf: the fused run with a schedule per filter; objects built
@@ -1745,7 +1747,7 @@ class BatchedEKF:
         raise KeyError(k)
       if self.eadims.get(k, 0):
         raise KalmanError(f"run_logs: kind {k} takes extra arguments, which a per-filter schedule does not carry")
-    Rd, per_entry = self._run_logs_noise(Rs, kd, T, diag_ok=self._has_batch_run_pf_rd() and not exact)
+    Rd, noise = self._run_logs_noise(Rs, kd, T, diag_ok=self._has_batch_run_pf_rd() and not exact)
     # every entry's dt from its filter's previous entry (or the filter's time in front of the first one): a forward fill along T
     has = kd > 0
     ft0 = self.filter_times()
@@ -1771,19 +1773,13 @@ class BatchedEKF:
       tx = torch.empty((T, N, self.dim_x), dtype=torch.float64, device=self.device) if trace else None
       tP = torch.empty((T, N, self.dim_err, self.dim_err), dtype=torch.float64, device=self.device) if trace else None
     fl = torch.zeros((T, N), dtype=torch.uint8, device=self.device) if flags else None
-    if per_entry == "diag":      # (only with the kernel and exact false: _run_logs_noise expands the variances otherwise)
-      self._call("batch_run_pf_rd", self._p(self.x), self._p(self.P), self._p(self.Q), self._p(kd), self._p(dts), T, self._p(zs), self._p(Rd), N,
-                 self.norm_quats, self._p(fl), self._p(tx), self._p(tP), self._stream())
-    elif per_entry and self._has_batch_run_pf_r() and not exact:
-      self._call("batch_run_pf_r", self._p(self.x), self._p(self.P), self._p(self.Q), self._p(kd), self._p(dts), T, self._p(zs), self._p(Rd), N,
-                 self.norm_quats, self._p(fl), self._p(tx), self._p(tP), self._stream())
-    elif per_entry:
-      self._run_logs_stepwise(kd, dts, zs, Rd, fl, tx, tP, symmetrise=not exact, per_entry=True)
-    elif self._has_batch_run_pf() and not exact:
-      self._call("batch_run_pf", self._p(self.x), self._p(self.P), self._p(self.Q), self._p(kd), self._p(dts), T, self._p(zs), self._p(Rd), N,
+    # (DIAG comes only with its kernel and exact false: _run_logs_noise expands the variances otherwise)
+    has = {TABLE: self._has_batch_run_pf, ENTRY: self._has_batch_run_pf_r, DIAG: self._has_batch_run_pf_rd}[noise]
+    if has() and not exact:
+      self._call(f"batch_run_pf{noise.sfx}", self._p(self.x), self._p(self.P), self._p(self.Q), self._p(kd), self._p(dts), T, self._p(zs), self._p(Rd), N,
                  self.norm_quats, self._p(fl), self._p(tx), self._p(tP), self._stream())
     else:
-      self._run_logs_stepwise(kd, dts, zs, Rd, fl, tx, tP, symmetrise=not exact)
+      self._run_logs_stepwise(kd, dts, zs, Rd, fl, tx, tP, symmetrise=not exact, per_entry=noise.per_entry)
     self.filter_time = ft_new
     self._ft_dev = None
     if self.rewind_to_keep > 0:
@@ -1791,22 +1787,14 @@ class BatchedEKF:
     self._keepalive = (kd, dts, Rd)
     return zs, tx, tP, fl
 
-  def _has_batch_run_pf_r(self):
-    fn = getattr(self._lib, f"{self.name}_has_batch_run_pf_r", None)
-    return fn is not None and int(fn()) == 1
-
-  def _has_batch_run_pf_rd(self):
-    fn = getattr(self._lib, f"{self.name}_has_batch_run_pf_rd", None)
-    return fn is not None and int(fn()) == 1
-
   def _run_logs_noise(self, Rs, kd, T, diag_ok=False):
-    """The observation noise of run_logs() on the device -> (Rd, per_entry).  Shared by the entries of every kind: the per-kind table
-    (num_kinds, zmax^2) of batch_run_pf, per_entry False.  Otherwise the kernel's per-entry layout (T, N, zmax^2) of batch_run_pf_r: row (t, i)
-    starts with the row-major (Z, Z) of entry (t, i), per_entry True.  A tensor or array in that layout is taken as it is (a device tensor of the
+    """The observation noise of run_logs() on the device -> (Rd, its NoiseMode).  Shared by the entries of every kind: the per-kind table
+    (num_kinds, zmax^2) of batch_run_pf, TABLE.  Otherwise the kernel's per-entry layout (T, N, zmax^2) of batch_run_pf_r: row (t, i)
+    starts with the row-major (Z, Z) of entry (t, i), ENTRY.  A tensor or array in that layout is taken as it is (a device tensor of the
     right dtype without a copy); a dict is gathered into it, every kind's rows where that kind occurs.
     Variances per entry -- a dict value (T, N, Z), or one array (T, N, zmax) -- stay rows of zmax doubles, the layout of batch_run_pf_rd, and
-    per_entry is "diag", where diag_ok (the library has that kernel and the run is not exact) and nothing in the dict needs a full matrix (no
-    (T, N, Z, Z) value, every shared value exactly diagonal); otherwise they are expanded into the (T, N, zmax^2) layout, per_entry True."""
+    the mode is DIAG, where diag_ok (the library has that kernel and the run is not exact) and nothing in the dict needs a full matrix (no
+    (T, N, Z, Z) value, every shared value exactly diagonal); otherwise they are expanded into the (T, N, zmax^2) layout, ENTRY."""
     torch = self._torch
     N, zmax = self.batch, max(self.zdims.values())
     ZZ = zmax * zmax
@@ -1828,12 +1816,12 @@ class BatchedEKF:
       if shape == (T, N, zmax) and zmax > 1:
         var = self._dev(Rs)
         if diag_ok:
-          return var, "diag"
-        return gather(ZZ, lambda k: embed(var[:, :, :self.zdims[k]], self.zdims[k])), True
+          return var, DIAG
+        return gather(ZZ, lambda k: embed(var[:, :, :self.zdims[k]], self.zdims[k])), ENTRY
       if shape not in ((T, N, zmax, zmax), (T, N, ZZ)):
         raise KalmanError(f"run_logs: Rs as one array is per entry, (T, N, zmax, zmax) = ({T}, {N}, {zmax}, {zmax}) or (T, N, zmax^2) = ({T}, {N}, {ZZ}), "
                           f"or its variances (T, N, zmax) = ({T}, {N}, {zmax}), got {shape}")
-      return self._dev(Rs).reshape(T, N, ZZ), True
+      return self._dev(Rs).reshape(T, N, ZZ), ENTRY
     shared, entry, var = {}, {}, {}
     for k in self.kinds:
       if k not in Rs:
@@ -1857,13 +1845,13 @@ class BatchedEKF:
       for i, k in enumerate(self.kinds):
         if k in shared:
           tab[i, :self.zdims[k] ** 2] = shared[k]
-      return self._dev(tab), False
+      return self._dev(tab), TABLE
     if var and not entry and diag_ok and all(not (m - np.diag(np.diag(m))).any() for m in (shared[k].reshape(self.zdims[k], -1) for k in shared)):
       return gather(zmax, lambda k: self._dev(var[k]) if k in var else
-                    self._dev(shared[k][::self.zdims[k] + 1].copy()).expand(T, N, self.zdims[k]) if k in shared else None), "diag"
+                    self._dev(shared[k][::self.zdims[k] + 1].copy()).expand(T, N, self.zdims[k]) if k in shared else None), DIAG
     return gather(ZZ, lambda k: self._dev(entry[k]).reshape(T, N, self.zdims[k] ** 2) if k in entry else
                   embed(self._dev(var[k]), self.zdims[k]) if k in var else
-                  self._dev(shared[k]).expand(T, N, self.zdims[k] ** 2) if k in shared else None), True
+                  self._dev(shared[k]).expand(T, N, self.zdims[k] ** 2) if k in shared else None), ENTRY
 
   def _run_logs_stepwise(self, kd, dts, zs, Rd, fl, tx, tP, symmetrise=True, per_entry=False):
     """run_logs() for a library without the fused kernel, and run_logs(exact=True): the same per-filter schedule, step by step.
