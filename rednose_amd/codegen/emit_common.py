@@ -234,7 +234,7 @@ def launch_predict(tiles):
 
 
 def _step_args(obs, do_predict, head=0):
-  """Arguments of a step kernel in its own order.  head=1 (the lane-per-filter family's tuning knob small_head): what the requests of a full tile need
+  """Arguments of a step kernel in its own order.  head=1 (the lane-per-filter family, emit_small._step_signature): what the requests of a full tile need
   comes first, within the 14 dwords that arrive preloaded in SGPRs, r_per_filter and norm_quats packed into one int (bits 0 and 1)."""
   if head:
     return (f"x, P, z, n, {'Q' if do_predict else 'nullptr'}, R, (r_per_filter != 0 ? 1 : 0) | (norm_quats != 0 ? 2 : 0), {obs}, "

@@ -21,13 +21,16 @@ Algebra emitted (reference lines in /root/reference/rednose/templates/ekf_c.c):
                   which is the same polynomial in the same inputs -- including the property that the
                   rounding error of B is cancelled to first order by the correction term.
 
-Where things are: predict_regs / update_regs / maha_regs print the algebra on registers.  kernels() strings the library's kernels together: k_predict,
-then step_kernel() for k_step_{kind}, k_stepc_{kind} (+ checkpoint) and -- through kinds_kernel() -- k_kinds (a kind per filter); it is made of
-named pieces (LDS images, TILE_LOOP, the tile requests with z last and a counted wait or all behind one wait, predict + pins, the split and the
-unsplit write-back, the non-finite test, the timeline stamps) of which k_predict, k_maha_{kind} and k_run take those that apply.  kind_cases()
-is the per-kind `switch` of k_kinds, k_run, k_run_blk and k_run_blk_tr.  _step_head() / predict_kernel() are the frame of the step kernels and of
-k_predict under the tuning knob small_head (default): the same pieces with the first tile's requests at the very top and the tile loop rotated.  The launch text of the step-granular kernels is emit_common's, bound to
-this family's TILES; launch_run is this family's own.
+Where things are: predict_regs / update_regs / maha_regs print the algebra on registers.  kernels() strings the library's kernels together:
+predict_kernel() for k_predict, then step_kernel() for k_step_{kind}, k_stepc_{kind} (+ checkpoint) and -- through kinds_kernel() -- k_kinds (a kind
+per filter).  The step kernels have ONE structure -- the first tile requested at the very top out of the preloaded arguments, Q by LDS-DMA among the
+requests, the observation tile last behind a counted wait, the tile loop rotated, x and the residual leaving ahead of P -- and step_kernel() joins it
+from the pieces above it: the timeline stamps (_stamp*), the request list (_step_requests, the one source of the requests' text and of the counted
+wait's operand), what happens once the tile has landed (_step_landed), the update with its write-back (_step_update per kind, _kinds_update mixed),
+the flags (_step_flags) and the signature with its host-order shim (_step_signature).  The smaller pieces (LDS images, TILE_LOOP / FIRST_TILE /
+NEXT_TILE, tile copies, pins, the non-finite test) also serve k_predict, k_maha_{kind} and k_run.  kind_cases() is the per-kind `switch` of k_kinds,
+k_run, k_run_blk and k_run_blk_tr.  The launch text of the step-granular kernels is emit_common's, bound to this family's TILES and to the preloaded
+argument order; launch_run is this family's own.
 """
 import functools
 
@@ -98,7 +101,7 @@ def predict_regs(spec, sym=False):
 def update_regs(spec, k, sym=False, split=False):
   """-> text of `update_<kind>_regs(x, P, z, R)`; returns the gate flag.  sym=True: `update_<kind>_regs_sym`, see predict_regs.
 
-  split=True (step-granular kernels, tuning knob small_split): `update_<kind>_regs_split(x, P, z, R, mid)` -- the same statements in the same
+  split=True (what the step-granular kernels call): `update_<kind>_regs_split(x, P, z, R, mid)` -- the same statements in the same
   order, but x and the residual are assigned where they are final, between the gain and the Joseph form, and `mid()` is called there: the
   kernel sends them on their way while the bulk of the update's arithmetic is still to come."""
   assert not (sym and split)
@@ -293,6 +296,16 @@ TILE_LOOP = """  const int64_t tiles = (n + 63) >> 6;
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const int64_t base = tile << 6;
     const int cnt = (n - base) < 64 ? (int)(n - base) : 64;"""
+# the rotated loop of the step kernels and k_predict: the first tile is requested in front of `for (;;)`, whose body ends with the next tile's requests
+FIRST_TILE = """  const int64_t tiles = (n + 63) >> 6;
+  int64_t tile = blockIdx.x;
+  if (tile >= tiles) return;
+  int64_t base = tile << 6;
+  int cnt = (n - base) < 64 ? (int)(n - base) : 64;"""
+NEXT_TILE = """    tile += gridDim.x;
+    if (tile >= tiles) break;
+    base = tile << 6;
+    cnt = (n - base) < 64 ? (int)(n - base) : 64;"""
 
 
 def _lds(flat=False, **doubles):
@@ -360,17 +373,15 @@ def kind_cases(spec, suffix, z, R, R_shared=None, extra="", ea_lane=None, ind=8)
 
 def kernels(spec):
   """Device functions + __global__ kernels of family S for every kind."""
-  tune = tuning.current()
-  waves, split, head = tune.small_waves, bool(tune.small_split), bool(tune.small_head)
-  kattr = f" __attribute__((amdgpu_waves_per_eu({waves}, {waves})))" if waves else ""
-  D, E = spec.dim_x, spec.dim_err
+  tline = bool(tuning.current().small_timeline)
+  E = spec.dim_err
   EE = E * E
   out = []
-  for sym in (False, True):          # full products for the step-granular kernels, symmetric arithmetic for the fused runs
+  for sym in (False, True):          # full products (and the split update) for the step-granular kernels, symmetric arithmetic for the fused runs
     ptxt, _ = predict_regs(spec, sym)
     out.append(ptxt)
     for k in spec.kinds:
-      utxt, _ = update_regs(spec, k, sym, split=split and not sym)
+      utxt, _ = update_regs(spec, k, sym, split=not sym)
       out.append(utxt)
   out.append(f"""
 // the fused multi-step kernels read (P + P^T) / 2 of the caller's covariance, once, as the state enters the registers
@@ -382,19 +393,8 @@ __device__ __forceinline__ void symmetrize_regs(double (&P)[{EE}]) {{
   }}
 }}
 """)
+  # (wait_but_tile is emitted although no kernel calls it: taking its two lines out changes every library's text and digest, a change of its own)
   out.append("""
-// What the step kernels use of the runtime beyond the tile copies: the counted wait and the per-filter dt as an LDS-DMA transfer
-// (templates/ekf_hip_rt.h).  A host build of this text (the kernels run lane by lane as threads, every copy synchronous) has nothing to wait for.
-#ifdef __HIP__
-template <int EPF> __device__ __forceinline__ void wait_but_tile(int cnt) { rn::async_wait_but_tile<EPF>(cnt); }
-__device__ __forceinline__ void lane_dt_request(const double* g_lane, double* lds, int lane) { (void)lane; rn::lane_double_g2l_async(g_lane, lds); }
-__device__ __forceinline__ double lane_dt(const double* lds, int lane) { return rn::lane_double_from_lds(lds, lane); }
-#else
-template <int EPF> inline void wait_but_tile(int) {}
-inline void lane_dt_request(const double* g_lane, double* lds, int lane) { lds[lane] = *g_lane; }
-inline double lane_dt(const double* lds, int lane) { return lds[lane]; }
-#endif
-""" if not head else """
 // What the step kernels use of the runtime beyond the tile copies: the counted waits, the per-filter dt and the shared Q as LDS-DMA transfers
 // (templates/ekf_hip_rt.h), and the point the instruction scheduler moves nothing across.  A host build of this text (the kernels run lane by
 // lane as threads, every copy synchronous) has nothing to wait for and nothing to hold.
@@ -415,50 +415,15 @@ inline void hold_order() {}
 #endif
 """)
   norm = norm_text(spec)
-  if tune.small_timeline:
+  if tline:
     out.append("__device__ unsigned long long g_tl[256 * 8 * 2];      // debug timeline (tuning knob small_timeline)")
-
-  out.append(predict_kernel(spec, norm) if head else f"""
-// ---- predict only: one launch propagates n filters by dt -------------------------------------------
-__global__ __launch_bounds__(64) void k_predict(double* __restrict__ gx, double* __restrict__ gP,
-    const double* __restrict__ gQ, const double* __restrict__ gdt, const double dt_scalar, const int64_t n,
-    const int norm_quats, const uint8_t* __restrict__ active) {{
-{_lds(x=D, P=EE)}
-{_lds(True, Q=EE)}
-  const int lane = threadIdx.x;
-  for (int i = lane; i < {EE}; i += 64) s_Q[i] = gQ[i];       // Q as LDS broadcast operands (36 SGPR pairs spilled otherwise)
-{TILE_LOOP}
-    {_tile_in(D, "gx", "s_x")}
-    {_tile_in(EE, "gP", "s_P")}
-    const double dt = (gdt != nullptr && lane < cnt) ? gdt[base + lane] : dt_scalar;
-    rn::async_wait();
-    rn::wave_lds_sync();
-    double x[{D}], P[{EE}];
-    rn::lds_to_regs<{D}>(s_x, lane, x);
-    rn::lds_to_regs<{EE}>(s_P, lane, P);
-    predict_regs(x, P, s_Q, dt);
-    {norm}
-    rn::wave_lds_sync();
-    // a masked-out filter (active[i] == 0: no observation for it in this call) keeps the record it came with: its lane
-    // does not overwrite the LDS image, so the coalesced write-back returns the loaded bytes
-    if (active == nullptr || (lane < cnt && active[base + lane] != 0)) {{
-      rn::regs_to_lds<{D}>(s_x, lane, x);
-      rn::regs_to_lds<{EE}>(s_P, lane, P);
-    }}
-    rn::wave_lds_sync();
-    {_tile_out(D, "gx", "s_x")}
-    {_tile_out(EE, "gP", "s_P")}
-    rn::wave_lds_sync();
-  }}
-}}
-""")
+  out.append(predict_kernel(spec, norm))
   # k_stepc_{kind}: the same kernel writing a CHECKPOINT on its way -- the observations as they came (cz) and the filtered pair (cx, cP): what the
   # orchestrators' rewind rings keep of every call (ekf_sym.cc:142-156, 191).  A kernel of its own, so that k_step_{kind} stays as it is.
-  knobs = dict(kattr=kattr, split=split, zwait=tune.small_zwait, tline=bool(tune.small_timeline), head=head and tune.small_zwait == 1)
-  out += [step_kernel(spec, norm, k, ckpt, **knobs) for k in spec.kinds for ckpt in (False, True)]
+  out += [step_kernel(spec, norm, k, ckpt, tline) for k in spec.kinds for ckpt in (False, True)]
   from rednose_amd.codegen import emit      # (emit imports this module: see its docstring)
   if emit.step_kinds(spec):
-    out.append(kinds_kernel(spec, norm, kattr, split, head))
+    out.append(kinds_kernel(spec, norm))
   if run_block(spec) > 0:          # blocked fused runs: k_run_blk (no trace) and k_run_blk_tr (filtered trace)
     out.append(run_kernel_blk(spec, norm))
     out.append(run_kernel_blk(spec, norm, trace=True))
@@ -470,140 +435,130 @@ __global__ __launch_bounds__(64) void k_predict(double* __restrict__ gx, double*
   return "\n".join(out)
 
 
-def kinds_kernel(spec, norm, kattr="", split=False, head=False):
-  """k_kinds: the step kernel in which every filter brings its own observation kind (kinds[i]).  The tile is loaded once -- z rows and per-filter
-  R at the strides of the fused run, zmax and zmax^2 --, predicted once, and a per-lane switch over the model's kinds calls update_{k}_regs:
-  a wavefront pays the sum of the kinds present among its 64 filters in arithmetic, and one trip through HBM.  A filter that is masked out, or
-  whose kind the model does not have, is not written back (flags 16 / 8): its lane leaves the LDS image as it was loaded.
-  The load order is that of small_zwait == 1 (z last, counted wait) whatever the knob says -- the knob's alternatives exist for the per-kind
-  kernels' A/B runs only --, s_R is allocated whether or not R comes per filter, and a shared R is read from the table inside the switch (one
-  load per kind present in the wavefront).  This family's kernel is covered by tests; its time has not been measured."""
-  return step_kernel(spec, norm, None, kattr=kattr, split=split, head=head)
+# ---- pieces of the step kernels (k_step_{kind}, k_stepc_{kind}, k_kinds), joined by step_kernel() ---------------------------------------------
+def _stamp(tline, i, pad="    "):
+  """Stamp i of the debug timeline (tuning knob small_timeline; tools/timeline.py small): shader cycles and the 100 MHz wall clock, in scalar registers."""
+  return f"\n{pad}if (tl_on) {{ tl_c[{i}] = __builtin_readcyclecounter(); tl_w[{i}] = wall_clock64(); }}" if tline else ""
 
 
-def step_kernel(spec, norm, k, ckpt=False, kattr="", split=False, zwait=1, tline=False, head=False):
-  """The step kernels, [predict +] update with the state round-tripping HBM once per launch: k_step_{kind} of kind k, k_stepc_{kind} (ckpt: the same
-  writing the call's checkpoint), and with k = None k_kinds (see kinds_kernel; x, z and P leave together there, after the switch).
-  `zwait`, `split`, `tline`, `head`: the tuning knobs small_zwait, small_split, small_timeline, small_head (head: see _step_head, which puts the
-  pieces made here into its own frame; it takes the request order of zwait == 1)."""
-  assert not head or zwait == 1
-  mixed = k is None
-  D, E = spec.dim_x, spec.dim_err
-  EE = E * E
-  Z = max(kk.zdim for kk in spec.kinds) if mixed else k.zdim
-  ZZ = Z * Z
-  kn = "k_kinds" if mixed else (f"k_stepc_{k.kind}" if ckpt else f"k_step_{k.kind}")
-  cargs = ", double* __restrict__ cx, double* __restrict__ cP, double* __restrict__ cz" if ckpt else ""
-  cz_store = f"\n    {_tile_out(Z, 'cz', 's_z')}      // the observations, before the residuals take their place" if ckpt else ""
-  cx_store = f"\n    {_tile_out(D, 'cx', 's_x')}" if ckpt else ""
-  cP_store = f"\n    {_tile_out(EE, 'cP', 's_P')}" if ckpt else ""
-
-  # ---- the timeline stamps (small_timeline; tools/timeline.py small): shader cycles and the 100 MHz wall clock, in scalar registers
-  def TL(i):
-    return f"\n    if (tl_on) {{ tl_c[{i}] = __builtin_readcyclecounter(); tl_w[{i}] = wall_clock64(); }}" if tline else ""
-  tl_pin = "\n" + _pin(EE, "P") if tline else ""      # stamped builds: a phase's arithmetic ends at its stamp
-  tl_decl = f"""
-    const bool tl_on = tile == blockIdx.x && blockIdx.x < 256;
-    unsigned long long tl_c[7] = {{0, 0, 0, 0, 0, 0, 0}}, tl_w[7] = {{0, 0, 0, 0, 0, 0, 0}};{TL(0)}""" if tline else ""
-  if tline and head:      # the entry stamp stands in front of the first tile's requests, outside the rotated loop; only the first tile is stamped
-    tl_decl = f"""
+def _stamp_decl(tline):
+  """The stamps' registers and the entry stamp, in front of the first tile's requests: outside the rotated loop, so only a workgroup's first tile is stamped."""
+  return f"""
   bool tl_on = blockIdx.x < 256;
-  unsigned long long tl_c[7] = {{0, 0, 0, 0, 0, 0, 0}}, tl_w[7] = {{0, 0, 0, 0, 0, 0, 0}};{TL(0).replace(chr(10) + "    ", chr(10) + "  ")}"""
-  tl_out = f"""{TL(6)}
+  unsigned long long tl_c[7] = {{0, 0, 0, 0, 0, 0, 0}}, tl_w[7] = {{0, 0, 0, 0, 0, 0, 0}};{_stamp(tline, 0, "  ")}""" if tline else ""
+
+
+def _stamp_out(tline):
+  """The last stamp, and lane 0 storing all seven when the tile is done (no store is in flight while a phase is timed)."""
+  return f"""{_stamp(tline, 6)}
     if (tl_on && lane == 0) {{
 #pragma unroll
       for (int i = 0; i < 7; i++) {{ g_tl[(blockIdx.x * 8 + i) * 2] = tl_c[i]; g_tl[(blockIdx.x * 8 + i) * 2 + 1] = tl_w[i]; }}
-    }}""" if tline else ""
-  if tline and head:
-    tl_out += "\n    tl_on = false;"
+    }}
+    tl_on = false;""" if tline else ""
 
-  # ---- the tile's requests, and what reads them out of LDS
-  tile_x, tile_P, tile_z = _tile_in(D, "gx", "s_x"), _tile_in(EE, "gP", "s_P"), _tile_in(Z, "gz", "s_z")
-  tile_R = "if (r_per_filter) " + _tile_in(ZZ, "gR", "s_R")
-  # the per-filter dt rides with the tiles (LDS-DMA, clamped inside a ragged tile: a lane without a filter stores nothing)
-  tile_dt = "if (DO_PREDICT && gdt != nullptr) lane_dt_request(gdt + base + (lane < cnt ? lane : cnt - 1), s_dt, lane);"
-  mask_note = ("// the mask and the kinds are requested behind the tiles: one round trip for all (see k_step_*)" if mixed else """\
-// masked-out filters (active[i] == 0) pass through untouched: x, P and z leave as they came, flag bit 4 is set.  The mask is requested
-    // behind the tiles: hipcc turns it into a lane mask at once, i.e. waits for it and for everything in front of it -- one round trip for all""")
-  act = f"""
-    {mask_note}
-    uint8_t act = 1;
-    if (active != nullptr) act = active[base + (lane < cnt ? lane : cnt - 1)];""" + ("""
-    const int kind = gkinds[base + (lane < cnt ? lane : cnt - 1)];""" if mixed else "")
-  regs = f"double x[{D}], P[{EE}], z[{Z}]{f', Rf[{ZZ}]' if mixed else ''};"
-  read_dt = "const double dt = (DO_PREDICT && gdt != nullptr) ? lane_dt(s_dt, lane) : dt_scalar;"
-  read_xP = f"""rn::lds_to_regs<{D}>(s_x, lane, x);
-    rn::lds_to_regs<{EE}>(s_P, lane, P);"""
-  read_zR = f"""rn::lds_to_regs<{Z}>(s_z, lane, z);
-    if (r_per_filter) rn::lds_to_regs<{ZZ}>(s_R, lane, {'Rf' if mixed else 'R'});"""
-  predict = f"""if (DO_PREDICT) {{
+
+def _loads(epf):
+  """global_load_lds instructions of tile_g2l_async<epf> on a full tile (rn::tile_async_loads)."""
+  return (32 * epf + 63) // 64
+
+
+def _step_requests(D, EE, Z, ZZ, mixed):
+  """The requests of a tile in issue order: [(text, transfers it issues on a full tile, first tile only, read by the predict or before it)].
+
+  This one list makes both the requests' text (_requests_text) and the operand of the counted wait (_in_flight): vmcnt retires in issue order, so
+  what may stay in flight under the predict is what stands behind the last request the predict reads -- the observation tile.  It goes last because
+  the update is the first to read it, after 42 LDS reads and the whole predict; in a stream it is also the slowest tile (a buffer nothing has touched
+  since it was written: HBM, while x and P were written by the previous launch and sit in the L2 / Infinity Cache).  The mask and the kinds are
+  ordinary loads in front of it.  (hipcc may move an ordinary load; whichever way it moves, no fewer transfers than counted are issued behind the
+  predict's last operand, so the wait can only be stronger than written, never weaker.)  A ragged tile goes through registers and waits for
+  everything, Q included.  Q comes by LDS-DMA into s_Q, once; a shared R is an ordinary load, once as well."""
+  lane_c = "base + (lane < cnt ? lane : cnt - 1)"      # clamped inside a ragged tile
+  shared_R = "" if mixed else f"""// a shared R: ordinary loads, once (it does not change from tile to tile), first used by the update
+  double R[{ZZ}];
+  if (!r_per_filter) {{
+#pragma unroll
+    for (int i = 0; i < {ZZ}; i++) R[i] = gR[i];
+  }}"""
+  return [(_tile_in(D, "gx", "s_x"), _loads(D), False, True), (_tile_in(EE, "gP", "s_P"), _loads(EE), False, True),
+          ("if (r_per_filter) " + _tile_in(ZZ, "gR", "s_R"), _loads(ZZ), False, True),
+          (shared_R, 0, True, True),
+          (f"if (DO_PREDICT) shared_request<{EE}>(gQ, s_Q, lane);", (2 * EE + 63) // 64, True, True),
+          ("hold_order();      // the arguments beyond the preloaded ones are first used below: their wait stands behind the requests above", 0, False, True),
+          # the per-filter dt rides with the tiles (LDS-DMA: a lane without a filter stores nothing)
+          (f"if (DO_PREDICT && gdt != nullptr) lane_dt_request(gdt + {lane_c}, s_dt, lane);", 2, False, True),
+          (f"if (active != nullptr) act = active[{lane_c}];", 0, False, True)] + ([(f"kind = gkinds[{lane_c}];", 0, False, True)] if mixed else []) + [
+          (_tile_in(Z, "gz", "s_z"), _loads(Z), False, False), ("hold_order();", 0, False, False)]
+
+
+def _requests_text(reqs, first, pad, tline):
+  """The requests of the first tile (in front of the loop) or of a later one (at the end of the loop's body), and the stamp behind them."""
+  return ("\n" + pad).join(text for text, _, first_only, _ in reqs if text and (first or not first_only)) + _stamp(tline, 1)
+
+
+def _in_flight(reqs):
+  """The operand of the counted wait: the transfers issued behind the last request the predict reads."""
+  last_needed = max(i for i, r in enumerate(reqs) if r[3])
+  return sum(r[1] for r in reqs[last_needed + 1:])
+
+
+def _step_landed(D, EE, Z, ZZ, mixed, norm, ckpt, tline):
+  """Behind the counted wait: x, P and dt from LDS to registers, the predict, pins that end its arithmetic there, the wait for the observation tile."""
+  pin_note = "" if mixed else "\n    // (the predict's arithmetic ends here: without the pins hipcc sinks it below the wait, into the update's)"
+  cz_store = f"\n    {_tile_out(Z, 'cz', 's_z')}      // the observations, before the residuals take their place" if ckpt else ""
+  return f"""
+    rn::wave_lds_sync();{_stamp(tline, 2)}
+    double x[{D}], P[{EE}], z[{Z}]{f', Rf[{ZZ}]' if mixed else ''};
+    const double dt = (DO_PREDICT && gdt != nullptr) ? lane_dt(s_dt, lane) : dt_scalar;
+    rn::lds_to_regs<{D}>(s_x, lane, x);
+    rn::lds_to_regs<{EE}>(s_P, lane, P);
+    if (DO_PREDICT) {{
       predict_regs(x, P, s_Q, dt);
       {norm}
-    }}"""
-  if zwait == 1:
-    # z last, counted wait.  vmcnt retires in issue order, so the tile that may stay in flight goes last: the observations are first read by the
-    # update, after 42 LDS reads and the whole predict; in a stream they are also the slowest tile (a buffer nothing has touched since it was
-    # written: HBM, while x and P were written by the previous launch and sit in the L2 / Infinity Cache)
-    pin_note = "" if mixed else "\n    // (the predict's arithmetic ends here: without the pins hipcc sinks it below the wait, into the update's)"
-    requests = f"""{tile_x}
-    {tile_P}
-    {tile_R}
-    {tile_dt}
-    {tile_z}{TL(1)}{act}
-    wait_but_tile<{Z}>(cnt);"""
-    landed = f"""
-    rn::wave_lds_sync();{TL(2)}
-    {regs}
-    {read_dt}
-    {read_xP}
-    {predict}{pin_note}
+    }}{pin_note}
 {_pin(D, "x")}
-{_pin(EE, "P")}{TL(4)}
+{_pin(EE, "P")}{_stamp(tline, 4)}
     rn::async_wait();
-    rn::wave_lds_sync();{TL(3)}{cz_store}
-    {read_zR}"""
-    load = requests + landed
-  else:
-    # all tiles, one wait; 0: the observations first (they are the slowest tile, see above), 2: between x and P
-    order = [tile_z, tile_R, tile_x, tile_P] if zwait == 0 else [tile_x, tile_R, tile_z, tile_P]
-    nl = "\n    "
-    behind = (32 * D + 63) // 64 + (32 * EE + 63) // 64 if zwait == 0 else (32 * EE + 63) // 64      # 16-byte requests behind the observations'
-    tlw = f"\n    if (tl_on && cnt == 64) rn::async_wait_but<{behind}>();{TL(3)}" if tline else ""
-    load = f"""{nl.join(order)}
-    {tile_dt}{TL(1)}{act}{tlw}
-    rn::async_wait();
-    rn::wave_lds_sync();{TL(2)}{cz_store}
-    {regs}
-    {read_dt}
-    {read_xP}
-    {read_zR}
-    {predict}{tl_pin}{TL(4)}"""
+    rn::wave_lds_sync();{_stamp(tline, 3)}{cz_store}
+    rn::lds_to_regs<{Z}>(s_z, lane, z);
+    if (r_per_filter) rn::lds_to_regs<{ZZ}>(s_R, lane, {'Rf' if mixed else 'R'});"""
 
-  # ---- the update and the write-back
-  x_z_out = f"""rn::wave_lds_sync();
+
+def _step_update(spec, k, norm, ckpt, tline):
+  """Update of kind k and the write-back: x and the residual are final before the Joseph form, the bulk of the update's arithmetic -- they leave
+  there (with the checkpoint's x and the non-finite test), P follows alone."""
+  D, EE, Z = spec.dim_x, spec.dim_err ** 2, k.zdim
+  # extra arguments are per observation, i.e. per filter of the batch: (n, len(ea)) row-major
+  ea = f", gea + (base + (lane < cnt ? lane : 0)) * {ea_count(k)}" if k.ea_sym is not None else ""
+  cx_store = f"\n      {_tile_out(D, 'cx', 's_x')}" if ckpt else ""
+  cP_store = f"\n    {_tile_out(EE, 'cP', 's_P')}" if ckpt else ""
+  tl_pin = "\n" + _pin(EE, "P") if tline else ""      # stamped builds: a phase's arithmetic ends at its stamp
+  return f"""const bool on = active == nullptr || (lane < cnt && act != 0);
+    int nf = 0;
+    int fl = update_{k.kind}_regs_split(x, P, z, R{ea}, [&]() {{
+      {norm}
+      rn::wave_lds_sync();
       if (on) {{
         rn::regs_to_lds<{D}>(s_x, lane, x);
         rn::regs_to_lds<{Z}>(s_z, lane, z);
       }}
       rn::wave_lds_sync();
       {_tile_out(D, "gx", "s_x")}
-      {_tile_out(Z, "gz", "s_z")}"""
-  all_out = f"""rn::wave_lds_sync();
-    if (on) {{
-      rn::regs_to_lds<{D}>(s_x, lane, x);
-      rn::regs_to_lds<{EE}>(s_P, lane, P);
-      rn::regs_to_lds<{Z}>(s_z, lane, z);
-    }}
-    rn::wave_lds_sync();
-    {_tile_out(D, "gx", "s_x")}
-    {_tile_out(EE, "gP", "s_P")}
-    {_tile_out(Z, "gz", "s_z")}{cx_store}{cP_store}
-    {{
+      {_tile_out(Z, "gz", "s_z")}{cx_store}
       {_flag_acc(D)}
-    }}"""
-  if mixed:
-    cases = kind_cases(spec, "_regs_split" if split else "_regs", "z", "Rf[i]", R_shared=lambda idx: f"gR[{idx * ZZ} + i]", extra=", []() {}" if split else "")
-    update = f"""const bool live = lane < cnt && act != 0;
+    }});{tl_pin}{_stamp(tline, 5)}
+    rn::wave_lds_sync();
+    if (on) rn::regs_to_lds<{EE}>(s_P, lane, P);
+    rn::wave_lds_sync();
+    {_tile_out(EE, "gP", "s_P")}{cP_store}"""
+
+
+def _kinds_update(spec, norm):
+  """Update of k_kinds and the write-back: a per-lane switch over the model's kinds, then x, P and the residual leave together.  A shared R is read
+  from the table inside the switch (one load per kind present in the wavefront)."""
+  D, EE, Z = spec.dim_x, spec.dim_err ** 2, max(k.zdim for k in spec.kinds)
+  cases = kind_cases(spec, "_regs_split", "z", "Rf[i]", R_shared=lambda idx: f"gR[{idx * Z * Z} + i]", extra=", []() {}")
+  return f"""const bool live = lane < cnt && act != 0;
     bool on = live;
     int fl = 0, nf = 0;
     if (live) {{
@@ -613,154 +568,97 @@ def step_kernel(spec, norm, k, ckpt=False, kattr="", split=False, zwait=1, tline
       }}
     }}
     {norm}
-    {all_out}"""
-  else:
-    # extra arguments are per observation, i.e. per filter of the batch: (n, len(ea)) row-major
-    ea = f", gea + (base + (lane < cnt ? lane : 0)) * {ea_count(k)}" if k.ea_sym is not None else ""
-    on = "const bool on = active == nullptr || (lane < cnt && act != 0);\n    int nf = 0;\n    "
-    if split:
-      # x and the residual are final before the Joseph form, the bulk of the update's arithmetic: they leave there, P follows alone
-      cx_store = cx_store.replace("\n    ", "\n      ")
-      update = f"""{on}int fl = update_{k.kind}_regs_split(x, P, z, R{ea}, [&]() {{
-      {norm}
-      {x_z_out}{cx_store}
+    rn::wave_lds_sync();
+    if (on) {{
+      rn::regs_to_lds<{D}>(s_x, lane, x);
+      rn::regs_to_lds<{EE}>(s_P, lane, P);
+      rn::regs_to_lds<{Z}>(s_z, lane, z);
+    }}
+    rn::wave_lds_sync();
+    {_tile_out(D, "gx", "s_x")}
+    {_tile_out(EE, "gP", "s_P")}
+    {_tile_out(Z, "gz", "s_z")}
+    {{
       {_flag_acc(D)}
-    }});{tl_pin}{TL(5)}
-    rn::wave_lds_sync();
-    if (on) rn::regs_to_lds<{EE}>(s_P, lane, P);
-    rn::wave_lds_sync();
-    {_tile_out(EE, "gP", "s_P")}{cP_store}"""
-    else:
-      update = f"""{on}int fl = update_{k.kind}_regs(x, P, z, R{ea});
-    {norm}{tl_pin}{TL(5)}
-    {all_out}"""
-  title = ("// ---- a kind per filter: [predict +] update of kinds[i], state round-trips HBM once per launch whatever the mix of kinds ------------" if mixed else
-           f"// ---- kind {k.kind}: [predict +] update{' + checkpoint' if ckpt else ''}, state round-trips HBM once per launch --------------------------")
-  shared_R = "" if mixed else f"""
-    // a shared R is requested in front of the tiles and first used behind the wait for all of them: an ordinary load, and at the first
-    // use of one hipcc waits for everything in flight
-    double R[{ZZ}];
-    if (!r_per_filter) {{
-#pragma unroll
-      for (int i = 0; i < {ZZ}; i++) R[i] = gR[i];
     }}"""
-  flags_out = f"if (flags != nullptr && lane < cnt) flags[base + lane] = (uint8_t)(on ? (fl | nf) : {'(live ? 8 : 16)' if mixed else '16'});{tl_out}"
-  if head:
-    return _step_head(locals())
-  return f"""
-{title}
-template <bool DO_PREDICT>
-__global__ __launch_bounds__(64){kattr} void {kn}(double* __restrict__ gx, double* __restrict__ gP,
-    double* __restrict__ gz, const double* __restrict__ gR, const int r_per_filter, {'const int32_t* __restrict__ gkinds' if mixed else 'const double* __restrict__ gea'},
-    const double* __restrict__ gQ, const double* __restrict__ gdt, const double dt_scalar, const int64_t n,
-    const int norm_quats, uint8_t* __restrict__ flags, const uint8_t* __restrict__ active{cargs}) {{
-{_lds(x=D, P=EE, z=Z, R=ZZ)}
-{_lds(True, Q=EE, dt=64)}
-  const int lane = threadIdx.x;
-  if (DO_PREDICT) {{
-    for (int i = lane; i < {EE}; i += 64) s_Q[i] = gQ[i];
-  }}
-{TILE_LOOP}{tl_decl}{shared_R}
-    {load}
-    {update}
-    {flags_out}
-    rn::wave_lds_sync();
-  }}
-}}
-"""
 
 
-NEXT_TILE = """    tile += gridDim.x;
-    if (tile >= tiles) break;
-    base = tile << 6;
-    cnt = (n - base) < 64 ? (int)(n - base) : 64;"""
-FIRST_TILE = """  const int64_t tiles = (n + 63) >> 6;
-  int64_t tile = blockIdx.x;
-  if (tile >= tiles) return;
-  int64_t base = tile << 6;
-  int cnt = (n - base) < 64 ? (int)(n - base) : 64;"""
+def _step_flags(mixed, tline):
+  """The flags of the tile's filters: what the update and the non-finite test set, or why the filter was left untouched; the stamps behind them."""
+  return f"if (flags != nullptr && lane < cnt) flags[base + lane] = (uint8_t)(on ? (fl | nf) : {'(live ? 8 : 16)' if mixed else '16'});{_stamp_out(tline)}"
 
 
-def _step_head(p):
-  """The step kernels with nothing in front of the first tile's requests (tuning knob small_head = 1); p: the pieces step_kernel made.
-
-  * Signature: gx, gP, gz, n, gQ, gR and `opts` (bit 0: r_per_filter, bit 1: norm_quats) are the first 13 dwords of the kernel arguments, which arrive
-    preloaded in SGPRs (rednose_amd/build.py: -amdgpu-kernarg-preload-count): the requests of x, P, a per-filter R and Q wait for no s_load.  The
-    other arguments are loaded at the top as before; their wait stands behind those requests, in front of the per-filter dt, the mask, the kinds.
-  * The tile loop is rotated: the first tile is requested outside it, its body is wait, compute, store, request the next tile.  hipcc cannot
-    hoist the loop's invariants (the addresses of the write-back, the lane masks of the ragged copies) in front of requests that stand outside
-    the loop, and hold_order() keeps its scheduler from moving anything across the end of the requests.
-  * Q comes by LDS-DMA with the tile, into s_Q, once (it does not change from tile to tile).  A shared R is an ordinary load behind the first
-    requests, once as well.
-  * One list of requests, in issue order, makes both the text and the operand of the counted wait: vmcnt retires in issue order, so what may stay
-    in flight under the predict is what stands behind the last request the predict reads -- the observation tile.  The mask and the kinds are
-    ordinary loads in front of it.  (hipcc may move an ordinary load; whichever way it moves, no fewer transfers than counted are issued behind
-    the predict's last operand, so the wait can only be stronger than written, never weaker.)  A ragged tile goes through registers and waits
-    for everything, Q included."""
-  D, EE, Z, ZZ, mixed = p["D"], p["EE"], p["Z"], p["ZZ"], p["mixed"]
-  TL = p["TL"]
-
-  def loads(epf):      # global_load_lds instructions of tile_g2l_async<epf> on a full tile (rn::tile_async_loads)
-    return (32 * epf + 63) // 64
-  mask = "if (active != nullptr) act = active[base + (lane < cnt ? lane : cnt - 1)];"
-  kinds = "kind = gkinds[base + (lane < cnt ? lane : cnt - 1)];"
-  # (text, transfers it issues on a full tile, first tile only, read by the predict or before it)
-  shared_R = "" if mixed else f"""// a shared R: ordinary loads, once (it does not change from tile to tile), first used by the update
-  double R[{ZZ}];
-  if (!r_per_filter) {{
-#pragma unroll
-    for (int i = 0; i < {ZZ}; i++) R[i] = gR[i];
-  }}"""
-  reqs = [(p["tile_x"], loads(D), False, True), (p["tile_P"], loads(EE), False, True), (p["tile_R"], loads(ZZ), False, True),
-          (shared_R, 0, True, True),
-          (f"if (DO_PREDICT) shared_request<{EE}>(gQ, s_Q, lane);", (2 * EE + 63) // 64, True, True),
-          ("hold_order();      // the arguments beyond the preloaded ones are first used below: their wait stands behind the requests above", 0, False, True),
-          (p["tile_dt"], 2, False, True), (mask, 0, False, True)] + ([(kinds, 0, False, True)] if mixed else []) + [
-          (p["tile_z"], loads(Z), False, False), ("hold_order();", 0, False, False)]
-  last_needed = max(i for i, r in enumerate(reqs) if r[3])
-  in_flight = sum(r[1] for r in reqs[last_needed + 1:])      # the operand of the counted wait
-
-  def requests(first, pad):
-    return ("\n" + pad).join(r[0] for r in reqs if r[0] and (first or not r[2])) + TL(1)
-  mask_note = ("// a filter that is masked out, or whose kind the model does not have, is not written back (flags 16 / 8)" if mixed else
-               "// masked-out filters (active[i] == 0) pass through untouched: x, P and z leave as they came, flag bit 4 is set")
+def _step_signature(kn, mixed, ckpt):
+  """Head of kernel `kn`.  gx, gP, gz, n, gQ, gR and `opts` (bit 0: r_per_filter, bit 1: norm_quats) are the first 13 dwords of the kernel arguments,
+  which arrive preloaded in SGPRs (rednose_amd/build.py: -amdgpu-kernarg-preload-count): the requests of x, P, a per-filter R and Q wait for no
+  s_load.  Host builds of this text (tests/test_emit_host*.py) call the kernels in the argument order of the C ABI: a shim in that order forwards."""
   obs = "const int32_t* __restrict__ gkinds" if mixed else "const double* __restrict__ gea"
-  kn, cargs = p["kn"], p["cargs"]
-  # host builds of this text (tests/test_emit_host*.py) call the kernels in the argument order of the C ABI
-  cnames = ", cx, cP, cz" if cargs else ""
-  host_order = f"""#ifndef __HIP__
+  cargs = ", double* __restrict__ cx, double* __restrict__ cP, double* __restrict__ cz" if ckpt else ""
+  cnames = ", cx, cP, cz" if ckpt else ""
+  return f"""#ifndef __HIP__
 template <bool DO_PREDICT> void {kn}(double* gx, double* gP, double* gz, const int64_t n, const double* gQ, const double* gR, const int opts, {obs.replace("__restrict__ ", "")}, const double* gdt, const double dt_scalar, uint8_t* flags, const uint8_t* active{cargs.replace("__restrict__ ", "")});
 template <bool DO_PREDICT> inline void {kn}(double* gx, double* gP, double* gz, const double* gR, const int r_per_filter, {obs.replace("__restrict__ ", "")}, const double* gQ, const double* gdt, const double dt_scalar, const int64_t n, const int norm_quats, uint8_t* flags, const uint8_t* active{cargs.replace("__restrict__ ", "")}) {{ {kn}<DO_PREDICT>(gx, gP, gz, n, gQ, gR, (r_per_filter != 0 ? 1 : 0) | (norm_quats != 0 ? 2 : 0), {'gkinds' if mixed else 'gea'}, gdt, dt_scalar, flags, active{cnames}); }}
-#endif"""
-  return f"""
-{p["title"]}
-{host_order}
+#endif
 template <bool DO_PREDICT>
-__global__ __launch_bounds__(64){p["kattr"]} void {kn}(double* __restrict__ gx, double* __restrict__ gP, double* __restrict__ gz, const int64_t n,
+__global__ __launch_bounds__(64) void {kn}(double* __restrict__ gx, double* __restrict__ gP, double* __restrict__ gz, const int64_t n,
     const double* __restrict__ gQ, const double* __restrict__ gR, const int opts, {obs},
-    const double* __restrict__ gdt, const double dt_scalar, uint8_t* __restrict__ flags, const uint8_t* __restrict__ active{cargs}) {{
-{_lds(x=D, P=EE, z=Z, R=ZZ)}
+    const double* __restrict__ gdt, const double dt_scalar, uint8_t* __restrict__ flags, const uint8_t* __restrict__ active{cargs}) {{"""
+
+
+def step_kernel(spec, norm, k, ckpt=False, tline=False):
+  """The step kernels, [predict +] update with the state round-tripping HBM once per launch: k_step_{kind} of kind k, k_stepc_{kind} (ckpt: the same
+  writing the call's checkpoint), and with k = None k_kinds (see kinds_kernel).  tline: the stamped build of the tuning knob small_timeline.
+
+  Nothing stands in front of the first tile's requests: what they need is in the preloaded arguments (_step_signature), the other arguments are
+  loaded at the top as before and their wait stands behind those requests, in front of the per-filter dt, the mask, the kinds.  The tile loop is
+  rotated: the first tile is requested outside it, its body is wait, compute, store, request the next tile.  hipcc cannot hoist the loop's
+  invariants (the addresses of the write-back, the lane masks of the ragged copies) in front of requests that stand outside the loop, and
+  hold_order() keeps its scheduler from moving anything across the end of the requests."""
+  mixed = k is None
+  D, EE = spec.dim_x, spec.dim_err ** 2
+  Z = max(kk.zdim for kk in spec.kinds) if mixed else k.zdim
+  kn = "k_kinds" if mixed else (f"k_stepc_{k.kind}" if ckpt else f"k_step_{k.kind}")
+  title = ("// ---- a kind per filter: [predict +] update of kinds[i], state round-trips HBM once per launch whatever the mix of kinds ------------" if mixed else
+           f"// ---- kind {k.kind}: [predict +] update{' + checkpoint' if ckpt else ''}, state round-trips HBM once per launch --------------------------")
+  mask_note = ("// a filter that is masked out, or whose kind the model does not have, is not written back (flags 16 / 8)" if mixed else
+               "// masked-out filters (active[i] == 0) pass through untouched: x, P and z leave as they came, flag bit 4 is set")
+  reqs = _step_requests(D, EE, Z, Z * Z, mixed)
+  update = _kinds_update(spec, norm) if mixed else _step_update(spec, k, norm, ckpt, tline)
+  kind_decl = "\n  int kind = 0;" if mixed else ""
+  return f"""
+{title}
+{_step_signature(kn, mixed, ckpt)}
+{_lds(x=D, P=EE, z=Z, R=Z * Z)}
 {_lds(True, Q=EE, dt=64)}
   const int lane = threadIdx.x;
   const int r_per_filter = opts & 1, norm_quats = opts & 2;
-{FIRST_TILE}{p["tl_decl"] if p["tline"] else ""}
-  uint8_t act = 1;{f"{chr(10)}  int kind = 0;" if mixed else ""}
-  {requests(True, "  ")}
+{FIRST_TILE}{_stamp_decl(tline)}
+  uint8_t act = 1;{kind_decl}
+  {_requests_text(reqs, True, "  ", tline)}
   for (;;) {{
     {mask_note}
-    wait_but_loads<{in_flight}>(cnt);{p["landed"]}
-    {p["update"]}
-    {p["flags_out"]}
+    wait_but_loads<{_in_flight(reqs)}>(cnt);{_step_landed(D, EE, Z, Z * Z, mixed, norm, ckpt, tline)}
+    {update}
+    {_step_flags(mixed, tline)}
     rn::wave_lds_sync();
 {NEXT_TILE}
-    {requests(False, "    ")}
+    {_requests_text(reqs, False, "    ", tline)}
   }}
 }}
 """
 
 
+def kinds_kernel(spec, norm):
+  """k_kinds: the step kernel in which every filter brings its own observation kind (kinds[i]).  The tile is loaded once -- z rows and per-filter
+  R at the strides of the fused run, zmax and zmax^2 --, predicted once, and a per-lane switch over the model's kinds calls update_{k}_regs_split:
+  a wavefront pays the sum of the kinds present among its 64 filters in arithmetic, and one trip through HBM.  A filter that is masked out, or
+  whose kind the model does not have, is not written back (flags 16 / 8): its lane leaves the LDS image as it was loaded.
+  s_R is allocated whether or not R comes per filter.  The kernel has no stamped build.  It is covered by tests; its time has not been measured."""
+  return step_kernel(spec, norm, None)
+
+
 def predict_kernel(spec, norm):
-  """k_predict with the prologue of small_head = 1 (see _step_head): its arguments but the mask are all within the preloaded ones as they stand."""
+  """k_predict, with the step kernels' prologue (see step_kernel): its arguments but the mask are all within the preloaded ones as they stand."""
   D, E = spec.dim_x, spec.dim_err
   EE = E * E
   dt = "dt = (gdt != nullptr && lane < cnt) ? gdt[base + lane] : dt_scalar;"
@@ -807,20 +705,9 @@ __global__ __launch_bounds__(64) void k_predict(double* __restrict__ gx, double*
 """
 
 
-def launch_step(kind, do_predict):
-  t = tuning.current()
-  return emit_common.launch_step(TILES, kind, do_predict, head=bool(t.small_head) and t.small_zwait == 1)
-
-
-def launch_step_ckpt(kind):
-  t = tuning.current()
-  return emit_common.launch_step_ckpt(TILES, kind, head=bool(t.small_head) and t.small_zwait == 1)
-
-
-def launch_kinds(do_predict):
-  return emit_common.launch_kinds(TILES, do_predict, head=bool(tuning.current().small_head))
-
-
+# the step kernels take their arguments in the preloaded order (_step_signature)
+launch_step, launch_step_ckpt, launch_kinds = (functools.partial(f, TILES, head=1) for f in (
+  emit_common.launch_step, emit_common.launch_step_ckpt, emit_common.launch_kinds))
 launch_predict = functools.partial(emit_common.launch_predict, TILES)
 launch_maha = functools.partial(emit_common.launch_maha, TILES, ea=False)      # this family's k_maha_{kind} has no extra-argument parameter
 

@@ -11,15 +11,7 @@ variants do not overwrite generated/).  What each alternative measured: profiles
   wide_fpw     filters per wavefront in the matrix phase (0 = 64 // dim_err)
   wide_lean    1 = covariance rows stay in LDS (register-lean structure, two wavefronts per SIMD)
   wide_lean_q  1 = the lean predict takes its column of Q from registers instead of an LDS copy
-  small_waves  amdgpu_waves_per_eu on the lane-per-filter step kernels
   small_max_e  largest error-state count served lane-per-filter
-  small_zwait  tile order / waits of the lane-per-filter step kernels: 1 = x, P, z with a counted wait (the observation tile stays in flight under
-               the predict), 2 = x, z, P and one wait, 0 = z, x, P and one wait
-  small_head   prologue of the lane-per-filter step kernels (k_step_*, k_stepc_*, k_kinds, k_predict): 1 = the first tile's requests are the first thing the
-               kernel does -- everything they need sits in the preloaded kernel arguments, Q rides with them as an LDS-DMA transfer, the tile loop is
-               rotated (wait, compute, store, request the next tile) --, 0 = Q through registers and the loop-invariant setup in front of the
-               tile loop.  Needs the request order of small_zwait=1: with another order the per-kind kernels keep prologue 0
-  small_split  1 = x and the residual leave the lane-per-filter step kernels between the gain and the Joseph form, 0 = with P at the end
   small_timeline  debug: phase stamps of the lane-per-filter step kernels, read back by {name}_debug_timeline (tools/timeline.py small)
   nt_trace     1 = nontemporal stores for the fused run's covariance trace (lane-group models)
   run_block    steps per block of the lane-per-filter fused run without trace (0 = auto by model size, -1 = that kernel is not emitted)
@@ -45,11 +37,7 @@ class Tuning:
   wide_fpw: int = 0
   wide_lean: int = 0
   wide_lean_q: int = 0
-  small_waves: int = 0
   small_max_e: int = 7
-  small_zwait: int = 1
-  small_split: int = 1
-  small_head: int = 1
   small_timeline: int = 0    # debug: lane 0 of the first 256 workgroups keeps s_memtime / the 100 MHz wall clock of seven phase boundaries of k_step / k_stepc
                              # in scalar registers and stores them when the tile is done (no store is in flight while a phase is timed)
   run_block: int = 0

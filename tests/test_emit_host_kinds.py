@@ -38,11 +38,10 @@ def _small_library(tmp_path, spec):
   helpers = "\n".join(_function_text(hdr, f) for f in ("lds_stride", "tile_g2l", "tile_l2g", "lds_to_regs", "regs_to_lds") + _SOLVERS)
   with tuning.using_model(spec):      # the text a library ships with: the model's tuning decides e.g. which flavour of update_{k}_regs the kernel calls
     text = emit_small.kernels(spec)
-    split = bool(tuning.current().small_split)
   funcs = text[:text.index("// ---- predict only")]      # predict_regs, update_{k}_regs[_split], and the host forms of wait_but_tile / lane_dt
   at = text.index("// ---- a kind per filter")
   kern = text[at:text.index("\n}\n", text.index("void k_kinds(", at)) + 3]
-  assert "void k_kinds(" in kern and ("_regs_split(" in kern) == split
+  assert "void k_kinds(" in kern and "_regs_split(" in kern
   src = "\n".join([_KERNEL_PRELUDE, helpers,
                    "template <int EPF> inline void tile_g2l_async(const double* g, int cnt, double* lds, int lane) { tile_g2l<EPF>(g, cnt, lds, lane); }",
                    "}  // namespace rn", funcs, kern, _RUN_GRID, _ENTRY])

@@ -1,4 +1,4 @@
-"""The prologue of the lane-per-filter step kernels (tuning knob small_head: the first tile requested before anything else, Q by LDS-DMA with it,
+"""The prologue of the lane-per-filter step kernels (the first tile requested before anything else, Q by LDS-DMA with it,
 the tile loop rotated) through the C ABI, every entry that launches k_step_* / k_stepc_* / k_kinds / k_predict, against the oracle:
 ragged first, only and last tiles, a batch large enough that a workgroup takes a second tile, shared / per-filter R, scalar / per-filter dt,
 mask and flags absent / present, dt = 0 (no Q request), Q on an address that is 8- but not 16-byte aligned, guard rows behind every array.

@@ -214,6 +214,45 @@ def test_blocked_fused_run_is_emitted_and_falls_back(tmp_path, monkeypatch):
   assert seen == [(True, True), (False, True)], seen       # second build: same family, without the blocked kernel
 
 
+def _lane_per_filter_model(name):
+  import examples.random_kf as R
+  from examples.attitude_kf import AttitudeKalman
+  from examples.kinematic_kf import KinematicKalman
+  from examples.kinematic6_kf import Kinematic6Kalman
+  return {"kinematic": KinematicKalman, "kinematic6": Kinematic6Kalman, "attitude": AttitudeKalman, "rand5": R.Random5Kalman}[name].model()
+
+
+@pytest.mark.parametrize("name", ["kinematic", "kinematic6", "attitude", "rand5"])      # Z = 1, Z > 1, odd E^2: the smallest that separate the cases
+def test_step_kernels_leave_exactly_the_observation_tile_in_flight(name):
+  """Every lane-per-filter step kernel (k_step_*, k_stepc_*, k_kinds) has ONE counted wait, wait_but_loads<N>, and N is the number of 16-byte
+  LDS-DMA requests of its observation tile alone -- (32 Z + 63) // 64 for 64 rows of Z doubles, worked out here from Z, not taken from the emitter:
+  exactly that tile may stay in flight under the predict."""
+  from rednose_amd.codegen import emit, emit_small
+  from rednose_amd.codegen.spec import build_spec
+  spec = build_spec(**_lane_per_filter_model(name))
+  assert emit.family(spec, ()) == "small"
+  text = emit_small.kernels(spec)
+  zdim = {f"{pre}{k.kind}": k.zdim for k in spec.kinds for pre in ("k_step_", "k_stepc_")}
+  if emit.step_kinds(spec, ()):
+    zdim["k_kinds"] = max(k.zdim for k in spec.kinds)
+  heads = list(re.finditer(r"^__global__ __launch_bounds__\(64\) void (k_stepc?_\d+|k_kinds)\(", text, flags=re.M))
+  assert sorted(m.group(1) for m in heads) == sorted(zdim), "one kernel per name"
+  for m in heads:
+    body = text[m.start():text.index("\n}\n", m.start())]
+    waits = re.findall(r"wait_but_loads<(\d+)>\(", body)
+    Z = zdim[m.group(1)]
+    assert waits == [str((32 * Z + 63) // 64)], f"{name} {m.group(1)} (Z = {Z}): counted waits {waits}"
+
+
+@pytest.mark.parametrize("knob", ["head", "zwait", "split", "waves"])
+def test_retired_step_kernel_knobs_are_unknown(monkeypatch, knob):
+  """The measured-and-lost alternatives of the lane-per-filter step kernels are gone: naming one in RN_TUNE is an error, not a silent default."""
+  from rednose_amd.codegen import tuning
+  monkeypatch.setenv("RN_TUNE", f"small_{knob}=0")
+  with pytest.raises(ValueError, match="unknown knob"):
+    tuning.current()
+
+
 def test_cffi_branch_of_load_code_runs_the_known_answers(monkeypatch):
   """`load_code` prefers cffi where it is importable -- which is every real rednose environment (rednose/helpers/__init__.py:3,18-31)
   -- and this image has none, so that branch (header lines -> ffi.cdef -> ffi.dlopen, ffi.cast marshalling in EKF_sym) never ran.

@@ -4,8 +4,9 @@ A change to the emitters that must leave every generated text as it is: run it w
 
   python tools/emit_digest.py OUT.txt [--tree OTHER_CHECKOUT] [--jobs N] [--with KNOB=V,..]
 
---with appends knob settings to every configuration's RN_TUNE and leaves the labels as they are: a knob whose value V is meant to reproduce a parent
-that does not know the knob (small_head=0) is checked by comparing that file with the parent's own, line by line."""
+--with appends knob settings to every configuration's RN_TUNE and leaves the labels as they are: a new knob whose value V is meant to reproduce a
+parent that does not know the knob is checked by comparing that file with the parent's own.  Configurations come and go with the knobs, so two
+digest files are compared by label: every line they share a label for must be the same line (`grep -Fxvf PARENT.txt BRANCH.txt` prints what is not)."""
 import argparse
 import hashlib
 import os
@@ -13,9 +14,7 @@ import sys
 import tempfile
 from concurrent.futures import ProcessPoolExecutor
 
-KNOBS = ("small_zwait=0", "small_zwait=2", "small_split=0", "small_zwait=0,small_split=0", "small_timeline=1", "small_timeline=1,small_zwait=0",
-         "small_timeline=1,small_zwait=2,small_split=0", "small_waves=2", "run_block=-1")      # of the lane-per-filter step kernels
-HEAD_KNOBS = ("small_head=0", "small_head=0,small_timeline=1", "small_head=0,small_split=0")      # the prologue before small_head (appended at the end, see configurations)
+KNOBS = ("small_timeline=1", "run_block=-1")      # of the lane-per-filter family: the stamped step kernels, the fused run without its blocked kernels
 FALLBACK_MODELS = {"force_wide": ("kinematic6", "attitude"), "no_run_blk": ("kinematic", "kinematic6"), "no_kinds": ("kinematic6", "kinematic9", "live"),
                    "no_model_defaults": ("live", "feature36"), "no_run2": ("live",), "no_tri": ("live",), "no_rts4": ("live",), "rts_one_wave": ("live",),
                    "no_rts": ("live",), "no_run": ("rand40", "feature36"),
@@ -41,9 +40,8 @@ def configurations():
   cfg = [(n, "", None) for n in examples.model_table()] + [(n, "exact_math=1", None) for n in examples.EXACT_NAMES]
   cfg += [(n, "", fb) for fb in emit.FALLBACKS for n in FALLBACK_MODELS[fb]]
   cfg += [(n, kn, None) for n in ("kinematic6", "attitude") for kn in KNOBS] + [("kinematic9", "wide_timeline=1", None)]
-  cfg += [(n, "", None) for n in GV_MODELS]      # appended to, never reordered: earlier digest files stay a prefix of later ones
+  cfg += [(n, "", None) for n in GV_MODELS]
   cfg += [(n, kn, None) for n, knobs in LANE_GROUP_KNOBS.items() for kn in knobs]
-  cfg += [(n, kn, None) for n in ("kinematic6", "attitude") for kn in HEAD_KNOBS]
   return cfg + [(n, kn, None) for n, knobs in RTS4_KNOBS.items() for kn in knobs]
 
 

@@ -183,7 +183,7 @@ def small():
   first 256 workgroups, for the two streams of profiles/tuning_notes.md (round 4, stages 4 and 5): every step with an observation buffer
   of its own that nothing has touched since it was written, and one buffer reused by every step.
 
-    RN_TUNE=small_timeline=1[,small_zwait=..,small_split=..] RN_GEN_DIR=/some/dir python tools/timeline.py small [batch]"""
+    RN_TUNE=small_timeline=1 RN_GEN_DIR=/some/dir python tools/timeline.py small [batch]"""
   import torch
   from examples import ensure_generated, GENERATED_DIR
   from examples.kinematic6_kf import Kinematic6Kalman as K6
