@@ -51,6 +51,8 @@ int kinematic6_has_batch_run_pf_rd(void);
 int kinematic6_batch_run_pf_rd(double *x, double *P, const double *Q, const int32_t *kinds, const double *dts, int64_t T, double *z, const double *R, int64_t n, int norm_quats, uint8_t *flags, double *trace_x, double *trace_P, void *stream);
 int kinematic6_has_tri_trace(void);
 int kinematic6_batch_rts(const double *xf, const double *Pf, const double *ts, int64_t T, const double *Q, int64_t n, int norm_quats, double *xs, double *Ps, const double *x_last, const double *P_last, void *stream);
+int kinematic6_has_batch_rts_pf(void);
+int kinematic6_batch_rts_pf(const double *xf, const double *Pf, const double *dts, const uint8_t *act, int64_t T, const double *Q, int64_t n, int norm_quats, double *xs, double *Ps, const double *x_last, const double *P_last, void *stream);
 void kinematic6_predict(double *in_x, double *in_P, double *in_Q, double dt);
 void kinematic6_update_1(double *in_x, double *in_P, double *in_z, double *in_R, double *in_ea);
 #ifdef __cplusplus

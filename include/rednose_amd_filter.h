@@ -315,6 +315,34 @@ extern "C" {
                                 int64_t T, double *z, const double *R, int64_t n, int norm_quats, uint8_t *flags, \
                                 double *trace_x, double *trace_P, void *stream);
 
+/* THE SMOOTHER WITH A SCHEDULE PER FILTER: the backward pass over the dense trace batch_run_pf writes, N ragged logs in ONE launch.
+ *   {name}_has_batch_rts_pf() == 1: the library has the kernel (every library with batch_rts whose model has no MSCKF window).  0: MSCKF
+ *   models, libraries without batch_rts, or a kernel that did not fit the register file -- batch_rts_pf then returns status 4 and nothing is
+ *   launched.
+ * All pointers are DEVICE pointers; alignment rules, status codes, the norm_quats bits and aliasing (xs == xf, Ps == Pf allowed) are those of
+ * batch_rts; T == 0 or n == 0 is a no-op that returns 0.  xf (T, n, D) / Pf (T, n, E, E): the dense trace (the row of an entry that did not step
+ * its filter is the pair the filter already had).  dts (T, n): the forward dt of every entry.  act (T, n): 1 where entry (t, i) stepped filter
+ * i -- its kind is a kind of the model, whether or not the gate rejected the update --, 0 for idle and unknown-kind entries, where dts is
+ * ignored.  Per filter i, with m its last entry with act == 1, backward step k relates rows k and k + 1:
+ *   act[k + 1, i] == 0   no predict happened between the two rows: the predicted pair of k + 1 IS the filtered pair of k and Ck = I -- for
+ *                        every model, also where predict(0) is not the identity (an idle entry is not a predict(0))
+ *   act[k + 1, i] == 1   the step of batch_rts with dt = dts[k + 1, i] (the identity-gain path for dt == 0 where the model has it)
+ *   start                the smoothed pair of row m is the PREDICTED pair of entry m (the reference's estimates[-1][0], [2]): recomputed from
+ *                        row m - 1 and dts[m, i], or row i of x_last / P_last when those are passed; step m - 1 therefore sees
+ *                        Pk1_n - Pk1_k = 0, as the reference's second-newest estimate does.  m == 0 and nothing passed: the filtered pair
+ *                        passes through (the T == 1 rule of batch_rts)
+ *   rows behind m        and every row of a filter without an act entry leave bit for bit as they came (copied, or in place rewritten with
+ *                        the same bits)
+ *   rows before the filter's first act entry f: step f - 1 is an ordinary full step with dts[f, i] -- it smooths the pair the filter started
+ *                        from --, the rows before it follow by identity steps.  (The reference has no counterpart: its estimates begin with
+ *                        the first observation.)
+ * Covariances are read as lower triangles, mirrored (see "Asymmetric covariances" above). */
+#define RN_DECLARE_BATCH_RTS_PF(name)                                                                            \
+  int RN_FN(name, has_batch_rts_pf)(void);                                                                       \
+  int RN_FN(name, batch_rts_pf)(const double *xf, const double *Pf, const double *dts, const uint8_t *act,       \
+                                int64_t T, const double *Q, int64_t n, int norm_quats, double *xs, double *Ps,   \
+                                const double *x_last, const double *P_last, void *stream);
+
 /* THE SAME RUN WITH A NOISE MATRIX PER LOG ENTRY.  A recorded log carries the noise of each observation (a GNSS fix with the receiver's
  * reported variance, an odometry frame with its own standard deviation); batch_run_pf knows one R per kind for the whole run.  Here
  * every entry (t, i) brings its own R, as every predict_and_update_batch(t, kind, z, R) call of the reference does.

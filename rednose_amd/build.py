@@ -89,7 +89,7 @@ def compile_filter(folder, name, extra_flags=(), verbose=False):
   if any("k_rts4" in k for k in usage):      # inline-assembly DPP operands: hipcc's hazard pass does not see them (dpp_hazards)
     dis = disassemble(lib)
     for k in usage:
-      if "k_rts4" in k:        # each kernel on its own (k_rts4, k_rts4_tri): <length><identifier>E of the Itanium mangling
+      if "k_rts4" in k:        # each kernel on its own (k_rts4, k_rts4_tri, k_rts4_pf): <length><identifier>E of the Itanium mangling
         hz = dpp_hazards(dis, kernel=f"{len(k)}{k}E") if dis is not None else []
         usage[k]["dpp_hazards"] = len(hz)
         if hz and verbose:
@@ -205,6 +205,9 @@ def kernel_resources(remarks):
         if mt and mt.group(2) is not None:
           targs.append(mt.group(2))
         cur = ident + (f"<{','.join(targs)}>" if targs else "")
+        # the hand-written smoothers, <class Model, bool PF>: the schedule-per-filter instantiation gets a row of its own
+        if ident in ("k_rts", "k_rts_group") and re.match(r"IN\w*?8RtsModelELb1EE", rest):
+          cur = ident + "<pf>"
       out[cur] = dict(vgprs=0, agprs=0, scratch=0, lds=0, vgpr_spill=0, occupancy=0)
       continue
     if cur is None:

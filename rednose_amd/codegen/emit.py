@@ -52,8 +52,12 @@ SMALL_MAX_E = 7    # lane-per-filter register budget: x, P and the update's temp
 #                      library without it ({name}_has_batch_run_pf_r() == 0, batch_run_pf_r returns ERR_UNSUPPORTED); k_run_pf and everything else stay
 #   no_run_pf_rd       the same run with a DIAGONAL noise per entry (k_run_dpf / k_run_dpf_tr) touches scratch memory or spills -> library without it
 #                      ({name}_has_batch_run_pf_rd() == 0, batch_run_pf_rd returns ERR_UNSUPPORTED); k_run_pf, k_run_rpf and everything else stay
+#   no_rts4_pf         k_rts4_pf (emit_rts4.kernel(pf=True), two wavefronts per SIMD) spilled, or one of its DPP reads follows the write of its source
+#                      too closely -> rn::k_rts_group<RtsModel, true> serves batch_rts_pf, as rn::k_rts_group serves batch_rts behind no_rts4
+#   no_rts_pf          the smoother with a schedule per filter (the PF = true instantiation of rn::k_rts / rn::k_rts_group) touches scratch memory or
+#                      spills -> library without it ({name}_has_batch_rts_pf() == 0, batch_rts_pf returns ERR_UNSUPPORTED); batch_rts and everything else stay
 FALLBACKS = ("force_wide", "no_model_defaults", "no_rts4", "rts_one_wave", "no_rts", "no_run2", "no_run", "no_run_blk", "no_tri", "no_kinds") + tuple(
-  m.fallback for m in NOISE_MODES)
+  m.fallback for m in NOISE_MODES) + ("no_rts4_pf", "no_rts_pf")
 KINDS_MAX = 16      # kinds of a model with a mixed-kind step: the Z table rn::k_timeline_push takes by value
 _active = frozenset()      # fallbacks of the emit() call in progress
 
@@ -101,6 +105,16 @@ def run_pf_r(spec, fallbacks=None):
 def run_pf_rd(spec, fallbacks=None):
   """has_run_pf() of the run with a DIAGONAL noise per entry (k_run_dpf)."""
   return has_run_pf(spec, DIAG, fallbacks)
+
+
+def rts_pf(spec, fallbacks=None):
+  """Does this library get the smoother with a schedule per filter (batch_rts_pf)?  Every model with a smoother and without an MSCKF window, in the
+  structure its batch_rts has: rn::k_rts<RtsModel, true> for lane-per-filter models, k_rts4_pf (emit_rts4.kernel(pf=True)) where batch_rts launches
+  k_rts4 (fallback no_rts4_pf: rn::k_rts_group's), rn::k_rts_group<RtsModel, true> for the other lane-group models."""
+  fb = _active if fallbacks is None else fallbacks
+  if "no_rts_pf" in fb or "no_rts" in fb or spec.N > 0 or any(k.He_sym is not None for k in spec.kinds):
+    return False
+  return spec.dim_main == spec.dim_x and spec.dim_main_err == spec.dim_err and spec.dim_err <= 64
 
 
 def _align2(n):
@@ -191,6 +205,8 @@ RUN_PARAMS = ("double *x, double *P, const double *Q, const int32_t *kinds, cons
               "uint8_t *flags, double *trace_x, double *trace_P, const double *ea, const int32_t *augment, void *stream")
 RUN_PF_PARAMS = ("double *x, double *P, const double *Q, const int32_t *kinds, const double *dts, int64_t T, double *z, const double *R, int64_t n, int norm_quats, "
                  "uint8_t *flags, double *trace_x, double *trace_P, void *stream")
+RTS_PF_PARAMS = ("const double *xf, const double *Pf, const double *dts, const uint8_t *act, int64_t T, const double *Q, int64_t n, int norm_quats, double *xs, "
+                 "double *Ps, const double *x_last, const double *P_last, void *stream")
 RTS_PARAMS = ("const double *xf, const double *Pf, const double *ts, int64_t T, const double *Q, int64_t n, int norm_quats, double *xs, double *Ps, "
               "const double *x_last, const double *P_last, void *stream")
 
@@ -225,6 +241,7 @@ def _select(spec):
   s.use_rts4 = wide and emit_rts4.applicable(spec) and tune.rts4 and "no_rts4" not in _active and "no_rts" not in _active
   s.use_tri = bool(s.use_run2 and s.use_rts4 and emit_run2.tri_trace(spec) and "no_tri" not in _active)
   s.has_rts = (wide or (spec.dim_main == spec.dim_x and spec.dim_main_err == spec.dim_err)) and "no_rts" not in _active
+  s.use_rts4_pf = bool(s.use_rts4 and s.has_rts and rts_pf(spec) and "no_rts4_pf" not in _active)
   return s
 
 
@@ -239,7 +256,8 @@ def _kernels(spec, s):
     if s.use_run2:
       parts.append(emit_run2.kernels(spec, tri=s.use_tri))
   parts.append(emit_wide2.maha_kernels(spec))
-  return ["\n".join(parts)] + ([emit_rts4.kernel(spec)] if s.use_rts4 else []) + ([emit_rts4.kernel(spec, tri=True)] if s.use_tri else [])
+  return (["\n".join(parts)] + ([emit_rts4.kernel(spec)] if s.use_rts4 else []) + ([emit_rts4.kernel(spec, tri=True)] if s.use_tri else []) +
+          ([emit_rts4.kernel(spec, pf=True)] if s.use_rts4_pf else []))
 
 
 def _routines(spec):
@@ -566,6 +584,23 @@ def _abi_rts(spec, s):
     rts("batch_rts", launch)
     if s.use_tri:
       rts("batch_rts_tri", emit_rts4.launch(spec, tri=True))
+  # The smoother with a schedule per filter: dts (T, n) and act (T, n) in place of ts (T).  The symbols exist in every library; without the
+  # kernel batch_rts_pf returns ERR_UNSUPPORTED.  The kernel has the structure of the library's batch_rts: k_rts4_pf beside k_rts4, else the
+  # PF = true instantiation of the hand-written smoother of the model's family (templates/ekf_hip_rts.h).
+  has = s.has_rts and rts_pf(spec)
+  a.fn("int", "has_batch_rts_pf", "void", f"return {int(has)};")
+  if has and s.use_rts4_pf:
+    body = _batched("n >= 0 && T >= 0 && xf && Pf && dts && act && Q && xs && Ps", ["xf", "Pf", "xs", "Ps", "x_last", "P_last"], emit_rts4.launch_pf(), empty="n == 0 || T == 0")
+  elif has:
+    M = spec.dim_main_err
+    fpw = (64 // (16 if M <= 16 else (32 if M <= 32 else 64))) if s.fam == "wide" else 2      # filters per wavefront
+    launch = f"""  const int64_t tiles = (n + {fpw - 1}) / {fpw};
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(rn::{'k_rts_group' if s.fam == 'wide' else 'k_rts'}<RtsModel, true>), dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
+                     xf, Pf, dts, T, Q, n, norm_quats, xs, Ps, x_last, P_last, act);"""
+    body = _batched("n >= 0 && T >= 0 && xf && Pf && dts && act && Q && xs && Ps", ["xf", "Pf", "xs", "Ps", "x_last", "P_last"], launch, empty="n == 0 || T == 0")
+  else:
+    body = _unsupported("batch_rts_pf: not generated for this model (MSCKF model, no smoother, or the kernel did not fit the register file)")
+  a.fn("int", "batch_rts_pf", RTS_PF_PARAMS, body)
   return a
 
 

@@ -137,14 +137,14 @@ def setprio(level, ind="      "):
 class Geometry:
   """What the phase builders of one kernel (k_rts4, tri: k_rts4_tri) share: sizes, the slot layout, where a row lives, the record provider."""
 
-  def __init__(self, spec, tri):
-    self.tri = tri
+  def __init__(self, spec, tri, pf=False):
+    self.tri, self.pf = tri, pf
     self.D, self.E = D, E = spec.dim_x, spec.dim_err
     self.EE = E * E
     self.TRI = E * (E + 1) // 2
     self.REC = self.TRI if tri else self.EE          # doubles per covariance record in memory
     self.ITT = -(-(FPW * self.TRI) // 64)       # packed elements per lane of a tile
-    self.kname = "k_rts4_tri" if tri else "k_rts4"
+    self.kname = "k_rts4_pf" if pf else ("k_rts4_tri" if tri else "k_rts4")
     self.R = rows_per_lane(spec)
     self.S = range(self.R)
     self.RS = -(-E // self.R)        # rows per slot: row r lives in slot r // RS of lane r % RS (22 states: 2 x 11 -- balanced slots keep the block lower
@@ -368,13 +368,14 @@ class Full:
     return (o + ["        }"] + opaque("        ", [f"rq{s}" for s in S]) + lower_rows(g, "ps", ind="        ")
             + ["        rn::wave_lds_sync();      // every lane has its rows: the image is free for the next step's burst"])
 
-  def store_predicted(self):
+  def store_predicted(self, also=""):
+    """(also: a further condition of the lane, k_rts4_pf's `&& fresh`)"""
     g = self.g
     o = [f"          double* __restrict__ po = Ps + ((k + 1) * n + base + gg) * {g.EE};      // the recomputed Pk1_k leaves mirrored from the block lower triangle the lanes hold"]
     for s in g.S:
-      o += [U, f"          for (int j = 0; j < {g.ncol(s)}; j++) {{ if (ok{s}) po[rr{s} * {g.E} + j] = a{s}[j]; }}"]
+      o += [U, f"          for (int j = 0; j < {g.ncol(s)}; j++) {{ if (ok{s}{also}) po[rr{s} * {g.E} + j] = a{s}[j]; }}"]
       if g.RS * s:
-        o += [U, f"          for (int j = 0; j < {g.RS * s}; j++) {{ if (ok{s}) po[j * {g.E} + rr{s}] = a{s}[j]; }}"]
+        o += [U, f"          for (int j = 0; j < {g.RS * s}; j++) {{ if (ok{s}{also}) po[j * {g.E} + rr{s}] = a{s}[j]; }}"]
     return o
 
   def final_decl(self):
@@ -505,12 +506,14 @@ def head(g):
   """title, what k_rts4_tri shares with the k_rts4 in front of it (macros, scalar phase), signature, LDS, per-launch values"""
   D, E, EE = g.D, g.E, g.EE
   o = [f"// ---- smoother, operands by row_newbcast: {GL} lanes x {g.R} rows per filter, {FPW} filters per wavefront (emit_rts4.py){' -- covariances as packed lower triangles' if g.tri else ''} ----"]
-  if not g.tri:
+  if g.pf:
+    o[0] = o[0][:-5] + " -- a schedule per filter: dts (T, n) in `ts`, ga (T, n) = 1 where the entry stepped its filter; see pf_step_flags() ----"
+  if not g.tri and not g.pf:
     o += [MACROS, f"constexpr int RTS4_SLOT = {g.lay.SLOT};", g.scal]
   return o + [f"""
 __global__ __launch_bounds__(64, 2) void {g.kname}(const double* __restrict__ xf, const double* __restrict__ Pf, const double* __restrict__ ts,
     const int64_t T, const double* __restrict__ gQ, const int64_t n, const int norm_quats, double* __restrict__ xs,
-    double* __restrict__ Ps, const double* __restrict__ xl, const double* __restrict__ Pl) {{
+    double* __restrict__ Ps, const double* __restrict__ xl, const double* __restrict__ Pl{", const unsigned char* __restrict__ ga" if g.pf else ""}) {{
   __shared__ __attribute__((aligned(16))) double s_I[{FPW} * {EE} + 2];          // the one matrix image per filter (see emit_rts4.py)
   __shared__ __attribute__((aligned(16))) double s_sl[{FPW} * RTS4_SLOT];        // x' = f(xk_k), F non-zeros, dt
   __shared__ __attribute__((aligned(16))) double s_xk[{FPW} * {D} + 2];          // xk_k
@@ -527,6 +530,10 @@ __global__ __launch_bounds__(64, 2) void {g.kname}(const double* __restrict__ xf
 def tile_prologue(g):
   """the tile's lanes and pointers, T == 1, xk_k of the first step, the carried rows and the newest pair where it is passed in"""
   D, E, EE, RS, S, REC = g.D, g.E, g.EE, g.RS, g.S, g.REC
+  pf_single = "" if not g.pf else f"""      // (a filter whose only entry is row 0: its predicted pair where it was passed in)
+      if (xl != nullptr) {{ rn::async_wait(); for (int i = lt; i < cnt * {D}; i += 64) {{ if (ga[base + i / {D}]) xs[base * {D} + i] = xl[base * {D} + i]; }} }}
+      if (Pl != nullptr) {{ rn::async_wait(); for (int i = lt; i < cnt * {REC}; i += 64) {{ if (ga[base + i / {REC}]) Ps[base * {REC} + i] = Pl[base * {REC} + i]; }} }}
+"""
   o = [f"""  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {{
     const int64_t base = tile * {FPW};
     const int cnt = (n - base) < {FPW} ? (int)(n - base) : {FPW};"""]
@@ -545,7 +552,7 @@ def tile_prologue(g):
   o += [f"""    if (T == 1) {{      // nothing to smooth, the single estimate's predicted pair is not available: the filtered pair passes through
       if (Ps != Pf) {{ for (int i = lt; i < cnt * {REC}; i += 64) Ps[base * {REC} + i] = Pf[base * {REC} + i]; }}
       if (xs != xf) {{ for (int i = lt; i < cnt * {D}; i += 64) xs[base * {D} + i] = xf[base * {D} + i]; }}
-      continue;
+{pf_single}      continue;
     }}
     // xk_k of the first step to process; every later one is committed to LDS by the step before it (nothing read from memory crosses the
     // loop's back edge in registers: hipcc waits for such a value with vmcnt(0) at the loop header -- behind the previous step's stores)
@@ -553,16 +560,40 @@ def tile_prologue(g):
     {g.rows_decl('ps', True)}      // rows of the smoothed covariance of step k + 1 (block lower triangle), carried from step to step; D = Pk1_n - Pk1_k inside a step"""]
   for s in S:
     o += [U, f"    for (int j = 0; j < {g.ncol(s)}; j++) ps{s}[j] = 0.0;"]
+  if g.pf:
+    return o + [f"""    // rows behind a filter's last entry pass through: the carried state starts as the raw newest row (it leaves with the first step), the newest
+    // covariance row is copied where the outputs are separate (every older row leaves as Pk_k + U with U = -0 until the recursion starts)
+    for (int i = lt; i < cnt * {D}; i += 64) s_xn[i] = xf[((T - 1) * n + base) * {D} + i];
+    if (Ps != Pf) {{ for (int i = lt; i < cnt * {REC}; i += 64) Ps[((T - 1) * n + base) * {REC} + i] = Pf[((T - 1) * n + base) * {REC} + i]; }}
+    bool started = false;      // an entry that stepped this lane's filter lies at or behind row k + 1
+    rn::wave_lds_sync();"""] + setprio(PRIO[2], "    ")
   o += ["    if (Pl != nullptr) {      // newest smoothed covariance := the predicted one of the last step as passed in (ekf_sym.py:658-659): through the image,",
         "      // like every later step's (lower triangle mirrored), and out to Ps[T - 1]"]
   o += g.rec.newest_in() + ["      rn::wave_lds_sync();"] + lower_rows(g, "ps", rc="rc") + ["      rn::wave_lds_sync();", "    }"]
   return o + ["    double dtc = ts[T - 1] - ts[T - 2];      // the step's time difference, read one step ahead (a scalar load's latency at the head of every step otherwise)"] + setprio(PRIO[2], "    ")
 
 
+def pf_step_flags(g):
+  """k_rts4_pf: what `first` and the identity test of k_rts4 become, per filter -- i.e. per 16-lane row; the compiler keeps such lane predicates as wave
+  masks in scalar registers.  Every DPP phase stays outside divergent code (EXEC full): the four rows walk the full path together and differ by selects.
+    st     entry k + 1 stepped the filter (act); an entry that did not is no predict: the rows of A and of Pk1_k are those of Pk_k, x' = xk_k
+    fresh  st and no entry behind k + 1 stepped it: the recursion starts here from the predicted pair just computed (or x_last / P_last)
+    ns     not started: row k + 1 lies behind the filter's last entry.  The carried state is the raw row (it leaves as it came), Ck = I and
+           U = -0, so Pk_n = Pk_k + U leaves with the bits of Pk_k
+    idn    an identity-gain step: Ck is forced to I, and T = Ck D, U = T Ck^T give U = D exactly (sums of exact zeros)"""
+  return [f"""      const bool st = ga[(k + 1) * n + base + gg] != 0;
+      const bool fresh = st && !started;
+      started = started || st;
+      const bool ns = !started;
+      const double dt = st ? ts[(k + 1) * n + base + gg] : 0.0;
+      const bool idn = !ns && !fresh && (!st{" || dt == 0.0" if g.dt0 else ""});
+      const bool eye = idn || ns;"""]
+
+
 def step_prologue(g):
   """the step's opaque lane and row indices, its store targets, its entries of a diagonal Q"""
   E, RS, S = g.E, g.RS, g.S
-  o = ["    for (int64_t k = T - 2; k >= 0; k--) {", "      const bool first = (k == T - 2);"]
+  o = ["    for (int64_t k = T - 2; k >= 0; k--) {"] + (pf_step_flags(g) if g.pf else ["      const bool first = (k == T - 2);"])
   o += opaque("      ", ["lb"], ["lt"], note2="         // opaque copy of the lane index: the copies' index arithmetic stays inside the step")
   o += opaque("      ", [f"rq{s}" for s in S], [f"rc{s}" for s in S], note="      // (same for the row indices: hoisted out of the step loop, the LDS addresses they feed were ~150 spilled registers)")
   o.append(f"      double* strash = s_trash + 2 * ((g * {GL - RS} + (ct >= {RS} ? ct - {RS} : ct)) % {max(1, FPW * (GL - RS))});      // (an idle lane's own 16 bytes of every row store: stores of many lanes to ONE address serialise)")
@@ -573,7 +604,7 @@ def step_prologue(g):
 
 def phase_a(g):
   return (["      // ---- A. filtered pair of step k: Pk_k -> image in one coalesced burst, xk_k -> LDS ----"] + g.rec.request_tile()
-          + ["      const double dt = dtc;", "      rn::wave_lds_sync();", "      RN_RTS_STAMP(1);"])
+          + ([] if g.pf else ["      const double dt = dtc;"]) + ["      rn::wave_lds_sync();", "      RN_RTS_STAMP(1);"])
 
 
 def identity_step(g):
@@ -584,7 +615,7 @@ def identity_step(g):
   rotations --,  Pk_n = Pk_k + (Pk1_n - Pk1_k)  evaluated as written.  No factorisation, no substitutions, no products: the step is one read and
   one write of the covariance.  dt is a scalar of the launch (ts is shared by the batch): the branch is uniform.  The recursion's first step always
   takes the full path (it also produces the newest pair).  Tuning knob rts_dt0 = 0 keeps the full solve on every step."""
-  if not g.dt0:
+  if not g.dt0 or g.pf:      # (k_rts4_pf: one path; a row at an identity step has Ck forced to I inside it)
     return []
   D, E, ind = g.D, g.E, "        "
   o = ["      if (dt == 0.0 && !first) {"] + renormalise(g, ind) + ["        rn::wave_lds_sync();"] + store_xs(g, ind)
@@ -608,7 +639,8 @@ def identity_step(g):
 
 def phase_b(g):
   return (["      // ---- B. f(xk_k) [renormalised like the forward pass], non-zeros of Fk: once per filter -> slot ----",
-           "      if (lead) scal_predict_s4(sxk, dt, sl, norm_quats & 1);"] + g.rec.land("      ")
+           "      if (lead) scal_predict_s4(sxk, dt, sl, norm_quats & 1);" if not g.pf else
+           f"      if (lead) {{ if (st) scal_predict_s4(sxk, dt, sl, norm_quats & 1); else {{ for (int i = 0; i < {g.D}; i++) sl[{g.lay.OFF_X} + i] = sxk[i]; }} }}      // (no predict happened: x' = xk_k)"] + g.rec.land("      ")
           + ["      rn::async_wait();", "      rn::wave_lds_sync();", "      RN_RTS_STAMP(2);"])
 
 
@@ -625,7 +657,8 @@ def phase_c(g):
   for s in S:      # the columns Fk leaves alone first: most of the row set is dead before the sums are formed
     o += [U, f"        for (int j = 0; j < {E}; j++) {{ if (" + (" && ".join(f"j != {jb}" for jb in g.busy) or "true") + f") sw{s}[j] = pf{s}[j]; }}"]
   o.append("        __builtin_amdgcn_sched_barrier(0);")
-  o += grouped(Fs, g.groups, "fp", "        ", lambda j, rt: [f"sw{s}[{j}] = {sum_terms(rt(cf, f'pf{s}[{kk}]') for kk, cf in Fs.row_nz(j))};" for s in S])
+  sel = (lambda s, j, v: f"st ? ({v}) : pf{s}[{j}]") if g.pf else (lambda s, j, v: v)
+  o += grouped(Fs, g.groups, "fp", "        ", lambda j, rt: [f"sw{s}[{j}] = {sel(s, j, sum_terms(rt(cf, f'pf{s}[{kk}]') for kk, cf in Fs.row_nz(j)))};" for s in S])
   return o + ["      }", "      rn::wave_lds_sync();"]
 
 
@@ -635,7 +668,8 @@ def predicted_covariance(g):
   o = [f"      {g.rows_decl('a', True)}      // rows of Pk1_k up to each slot's last row (symmetric: the block lower triangle is all anything reads), then its L D L^T factor (unit lower triangle, reciprocal pivots on the diagonal)"]
   for s in S:
     o += ["      {", f"        double col[{E}];", U, f"        for (int m = 0; m < {E}; m++) col[m] = sI[m * {E} + rq{s}];      // column of A = row of Fk Pk_k"]
-    o += grouped(Fs, g.groups, f"fq{s}_", "        ", lambda j, rt, s=s: ([f"a{s}[{j}] = {sum_terms(rt(cf, f'col[{m}]') for m, cf in Fs.row_nz(j))};"] if j < ncol(s) else []))
+    sel = (lambda j, v: f"st ? ({v}) : col[{j}]") if g.pf else (lambda j, v: v)
+    o += grouped(Fs, g.groups, f"fq{s}_", "        ", lambda j, rt, s=s, sel=sel: ([f"a{s}[{j}] = {sel(j, sum_terms(rt(cf, f'col[{m}]') for m, cf in Fs.row_nz(j)))};"] if j < ncol(s) else []))
     o += [f"        a{s}[{j}] = col[{j}];" for j in range(ncol(s)) if j not in g.busy] + ["      }"]
   o.append("      if (qdiag) {")
   for s in S:
@@ -652,7 +686,37 @@ def predicted_covariance(g):
   return o + ["      }", "      RN_RTS_STAMP(4);"]
 
 
+def phase_d_pf(g):
+  """k_rts4_pf: the recursion starts per filter (pf_step_flags)"""
+  D, E, EE, S = g.D, g.E, g.EE, g.S
+  o = [f"""      // ---- D. recursion start of the filters that are `fresh` / difference matrix (the image keeps A) ----
+      if (__any(fresh)) {{
+        if (live && fresh) {{      // newest estimate := the predicted pair of the filter's last entry (passed in, or recomputed just now): ekf_sym.py:658-659
+          const int cf = lb % {GL};
+          if (xl != nullptr) {{ for (int i = cf; i < {D}; i += {GL}) sxn[i] = xl[(base + lb / {GL}) * {D} + i]; }}
+          else {{ for (int i = cf; i < {D}; i += {GL}) sxn[i] = sl[{g.lay.OFF_X} + i]; }}
+        }}
+        rn::async_wait();      // row k + 1 left raw with the step before (Pk_k + U, U = -0): that store has landed before this one is issued
+        if (Pl == nullptr) {{"""]
+  o += g.rec.store_predicted(also=" && fresh") + ["        } else {", f"          double* __restrict__ po = Ps + ((k + 1) * n + base + gg) * {EE};",
+                                                   f"          const double* __restrict__ pi = Pl + (base + gg) * {EE};"]
+  for s in S:
+    o += [U, f"          for (int j = 0; j < {E}; j++) {{ if (ok{s} && fresh) po[rr{s} * {E} + j] = pi[rr{s} * {E} + j]; }}",
+          U, f"          for (int j = 0; j < {g.ncol(s)}; j++) {{ if (fresh) ps{s}[j] = pi[{E} * max(rq{s}, j) + min(rq{s}, j)]; }}      // (lower triangle mirrored, like every carried row)"]
+  o += ["        }", "      }", "      rn::wave_lds_sync();"]
+  o += [ln.replace("if (lead && (norm_quats & 2))", "if (lead && (norm_quats & 2) && started)") for ln in renormalise(g, "      ")] + ["      rn::wave_lds_sync();"]
+  o += ["      {"] + store_xs(g, "        ") + ["      }"]
+  o += [f"""      // D = Pk1_n - Pk1_k; a fresh row that recomputed its predicted pair has Pk1_n = Pk1_k: D = 0
+      const bool dzero = fresh && Pl == nullptr;
+      if (lead) inv_err_fun(sl + {g.lay.OFF_X}, sxn, sdv);"""]
+  for s in S:
+    o += [U, f"      for (int j = 0; j < {g.ncol(s)}; j++) {{ ps{s}[j] = dzero ? 0.0 : fma(-1.0, a{s}[j], ps{s}[j]); rn::pin(ps{s}[j]); }}"]
+  return o + ["      RN_RTS_STAMP(5);"]
+
+
 def phase_d(g):
+  if g.pf:
+    return phase_d_pf(g)
   D, S = g.D, g.S
   o = [f"""      // ---- D. recursion start / difference matrix (the image keeps A: the substitutions take their right-hand sides from it) ----
       if (first) {{
@@ -705,7 +769,10 @@ def phase_f(g):
     # y[m] *= 1 / d_m as ONE multiply-add with the reciprocal pivot broadcast by the instruction itself (0 + (1 / d_m) y[m]: the product, bit for bit)
     o += [f"        {{ double t_ = 0.0; RN4_FMAC(t_, a{slot_of(m)}[{m}], y[{m}], {lane_of(m)}); y[{m}] = t_; }}" for m in range(E)]
     o += [f"        RN4_FNMAC(y[{i}], a{slot_of(m)}[{i}], y[{m}], {lane_of(m)});" for m in range(E - 1, 0, -1) for i in range(m - 1, -1, -1)]
-    o += [U, f"        for (int j = 0; j < {E}; j++) sw{s}[j] = y[j];      // row of Ck (each lane overwrites the row it read; idle lanes: the trash row)", "      }"]
+    if g.pf:
+      o += [U, f"        for (int j = 0; j < {E}; j++) sw{s}[j] = eye ? (rq{s} == j ? 1.0 : 0.0) : y[j];      // row of Ck, the identity's where the filter's step is an identity-gain step", "      }"]
+    else:
+      o += [U, f"        for (int j = 0; j < {E}; j++) sw{s}[j] = y[j];      // row of Ck (each lane overwrites the row it read; idle lanes: the trash row)", "      }"]
   return o + ["      rn::wave_lds_sync();", "      RN4_SETTLE();      // (the rows of D were pinned where they were formed)"]
 
 
@@ -756,7 +823,7 @@ def phase_i(g):
       o += g.rec.final_request() + request_xnext(g, "      ", "le") + ["      __builtin_amdgcn_sched_barrier(0);"]
     o += ["      {", f"        double u[{c1 - c0}];", U, f"        for (int j = 0; j < {c1 - c0}; j++) u[j] = 0.0;"]
     o += [f"        RN4_FMAC(u[{j - c0}], ck{q}[{kk}], t{s}[{kk}], {g.lane_of(j)});" for kk in range(E) for j in range(c0, c1)]
-    o += [U, f"        for (int j = 0; j < {c1 - c0}; j++) sw{s}[{c0} + j] = u[j];", "      }", "      __builtin_amdgcn_sched_barrier(0);"]
+    o += [U, f"        for (int j = 0; j < {c1 - c0}; j++) sw{s}[{c0} + j] = {'ns ? -0.0 : ' if g.pf else ''}u[j];", "      }", "      __builtin_amdgcn_sched_barrier(0);"]
   return o + ["      rn::wave_lds_sync();", "      RN_RTS_STAMP(9);"] + setprio(PRIO[2])
 
 
@@ -772,30 +839,48 @@ def phase_j(g):
         for (int i = 0; i < {E}; i++) delta[i] = sdv[i];
         err_fun(xa, delta, xnew);
 #pragma unroll
-        for (int i = 0; i < {D}; i++) sxn[i] = xnew[i];       // xk_n: becomes xk1_n of the next (older) step
+        for (int i = 0; i < {D}; i++) sxn[i] = {"ns ? xa[i] : " if g.pf else ""}xnew[i];       // xk_n: becomes xk1_n of the next (older) step
       }}
-      dtc = k > 0 ? ts[k] - ts[k - 1] : 0.0;
-      rn::wave_lds_sync();      // the lead lanes have read xk_k: the buffer takes the next step's"""]
+{"" if g.pf else "      dtc = k > 0 ? ts[k] - ts[k - 1] : 0.0;" + chr(10)}      rn::wave_lds_sync();      // the lead lanes have read xk_k: the buffer takes the next step's"""]
   o += commit_xnext(g, "      ", "le") + g.rec.final_pass() + ["      rn::wave_lds_sync();"]
   o += opaque("      ", [f"rq{s}" for s in g.S], note2="      // (fresh addresses: those of the step's first row read are not worth registers across the step)")
   return o + lower_rows(g, "ps") + ["      rn::wave_lds_sync();      // every lane has its rows: the image is free for the next step's burst", "      RN_RTS_STAMP(10);", "    }"]
 
 
 def epilogue(g):
-  o = ["    // ---- the oldest smoothed state goes out un-normalised (ekf_sym.py:665-667 never reaches it); its covariance left above ----", "    {"]
+  o = []
+  if g.pf:
+    o = [f"""    if ((xl != nullptr || Pl != nullptr) && __any(live && !started && ga[base + gg] != 0)) {{      // a filter whose only entry is row 0: its predicted pair where it was passed in
+      const bool only0 = live && !started && ga[base + gg] != 0;
+      if (xl != nullptr && only0) {{ for (int i = c; i < {g.D}; i += {GL}) sxn[i] = xl[(base + gg) * {g.D} + i]; }}
+      if (Pl != nullptr) {{
+        rn::async_wait();      // row 0 left with the last step: before this store
+        double* __restrict__ po = Ps + (base + gg) * {g.EE};
+        const double* __restrict__ pi = Pl + (base + gg) * {g.EE};"""]
+    for s in g.S:
+      o += [U, f"        for (int j = 0; j < {g.E}; j++) {{ if (ok{s} && only0) po[rr{s} * {g.E} + j] = pi[rr{s} * {g.E} + j]; }}"]
+    o += ["      }", "      rn::wave_lds_sync();", "    }"]
+  o += ["    // ---- the oldest smoothed state goes out un-normalised (ekf_sym.py:665-667 never reaches it); its covariance left above ----", "    {"]
   o += opaque("      ", ["lz"], ["lane"]) + [f"      for (int i = lz; i < cnt * {g.D}; i += 64) xs[base * {g.D} + i] = s_xn[i];", "    }"]
   return o + ["    rn::wave_lds_sync();", "  }", "}"]
 
 
-def kernel(spec, tri=False):
+def kernel(spec, tri=False, pf=False):
   """tri=True: `k_rts4_tri` -- the same recursion on a trace whose covariances are PACKED lower triangles (row-major, E (E + 1) / 2 doubles:
   what batch_run_tri writes): Pf, Ps and Pl are (.., E (E + 1) / 2) arrays.  The kernel's matrix image stays E x E; a packed element goes to /
   comes from the image's LOWER position (row of a packed index: a byte table in LDS, filled once per launch), which is all the kernel reads
   of a covariance anyway (the contract of batch_rts) -- the upper-right exchange of the identity-gain step and the mirroring of U drop out."""
-  g = Geometry(spec, tri)
+  g = Geometry(spec, tri, pf)
   phases = (head, tile_prologue, step_prologue, phase_a, identity_step, phase_b, phase_c, predicted_covariance, phase_d, phase_e, phase_f, phase_h, phase_i,
             phase_j, epilogue)
   return "\n".join(ln for phase in phases for ln in phase(g))
+
+
+def launch_pf():
+  """k_rts4_pf (kernel(spec, pf=True)): the smoother with a schedule per filter; `ts` carries dts (T, n)."""
+  return f"""  const int64_t tiles = (n + {FPW - 1}) / {FPW};
+  hipLaunchKernelGGL(k_rts4_pf, dim3(rn::grid_for_tiles(tiles)), dim3(64), 0, (hipStream_t)stream,
+                     xf, Pf, dts, T, Q, n, norm_quats, xs, Ps, x_last, P_last, act);"""
 
 
 def launch(spec, tri=False):

@@ -81,6 +81,15 @@ def gen_code(folder, name, f_sym, dt_sym, x_sym, obs_eqs, dim_x, dim_err, eskf_p
                                          "without it") if pf_bad else (usage, bad)
       for noise in reversed(NOISE_MODES):
         usage, bad = drop(noise)
+      if "k_rts4_pf" in bad:
+        # like no_rts4 for batch_rts: the lane-group smoother's per-filter instantiation serves batch_rts_pf instead
+        usage, bad = fall_back("no_rts4_pf", "the register-broadcast smoother with a schedule per filter spills under its two-wavefronts-per-SIMD budget (or a DPP "
+                                             "read follows the write of its source too closely): lane-group smoother instead")
+      rts_pf_bad = [k for k in bad if k in ("k_rts<pf>", "k_rts_group<pf>")]
+      if rts_pf_bad:
+        # batch_rts is intact: the smoother with a schedule per filter alone is dropped ({name}_has_batch_rts_pf() == 0), before anything
+        # below could answer for it with a fallback of the whole smoother
+        usage, bad = fall_back("no_rts_pf", f"the smoother with a schedule per filter {rts_pf_bad} does not fit the register file: library without it")
       if "k_run_blk" in bad or "k_run_blk_tr" in bad:
         usage, bad = fall_back("no_run_blk", "a blocked fused run spills registers: the step-at-a-time k_run serves fused runs instead")
         for noise in reversed(NOISE_MODES):
@@ -1748,21 +1757,8 @@ class BatchedEKF:
       if self.eadims.get(k, 0):
         raise KalmanError(f"run_logs: kind {k} takes extra arguments, which a per-filter schedule does not carry")
     Rd, noise = self._run_logs_noise(Rs, kd, T, diag_ok=self._has_batch_run_pf_rd() and not exact)
-    # every entry's dt from its filter's previous entry (or the filter's time in front of the first one): a forward fill along T
-    has = kd > 0
     ft0 = self.filter_times()
-    idx = torch.where(has, torch.arange(T, device=self.device)[:, None], torch.full((1, 1), -1, dtype=torch.int64, device=self.device))
-    last = torch.cummax(idx, dim=0).values                                         # (T, N): the latest entry of filter i up to step t, -1: none yet
-    prev = torch.cat([torch.full((1, N), -1, dtype=torch.int64, device=self.device), last[:-1]], 0)
-    t_prev = torch.where(prev >= 0, tt.gather(0, prev.clamp(min=0)), ft0[None, :])
-    dts = torch.where(has, torch.nan_to_num(tt - t_prev, nan=0.0), torch.zeros_like(tt)).contiguous()
-    bad = has & (torch.isnan(tt) | (tt < t_prev))
-    if bool(bad.any()):
-      t_, i_ = (int(v) for v in bad.nonzero()[0])
-      if bool(torch.isnan(tt[t_, i_])):
-        raise KalmanError(f"run_logs: filter {i_}, step {t_}: kind {int(kd[t_, i_])} without a time (ts is NaN there; NaN marks idle entries, whose kind is <= 0)")
-      raise KalmanError(f"run_logs: filter {i_}, step {t_}: time {float(tt[t_, i_])} lies before the filter's previous time {float(t_prev[t_, i_])} "
-                        "-- sort the log: a fused run does not rewind")
+    dts, last = self._log_dts(tt, kd, ft0, "run_logs")
     ft_new = torch.where(last[-1] >= 0, tt.gather(0, last[-1:].clamp(min=0))[0], ft0).contiguous()
     zs = self._dev(zs, (T, N, zmax))
     if out is not None:
@@ -1786,6 +1782,27 @@ class BatchedEKF:
       self.reset_rewind()
     self._keepalive = (kd, dts, Rd)
     return zs, tx, tP, fl
+
+  def _log_dts(self, tt, kd, ft0, who):
+    """Every entry's dt from its filter's previous entry (or the filter's time ft0 in front of the first one; NaN there: dt = 0): a forward
+    fill along T, shared by run_logs and rts_smooth_logs -> (dts (T, N), last (T, N): the latest entry of filter i up to step t, -1: none yet).
+    Raises KalmanError for a log that is not in time order and for a real entry without a time."""
+    torch = self._torch
+    T, N = tt.shape
+    has = kd > 0
+    idx = torch.where(has, torch.arange(T, device=self.device)[:, None], torch.full((1, 1), -1, dtype=torch.int64, device=self.device))
+    last = torch.cummax(idx, dim=0).values
+    prev = torch.cat([torch.full((1, N), -1, dtype=torch.int64, device=self.device), last[:-1]], 0)
+    t_prev = torch.where(prev >= 0, tt.gather(0, prev.clamp(min=0)), ft0[None, :])
+    dts = torch.where(has, torch.nan_to_num(tt - t_prev, nan=0.0), torch.zeros_like(tt)).contiguous()
+    bad = has & (torch.isnan(tt) | (tt < t_prev))
+    if bool(bad.any()):
+      t_, i_ = (int(v) for v in bad.nonzero()[0])
+      if bool(torch.isnan(tt[t_, i_])):
+        raise KalmanError(f"{who}: filter {i_}, step {t_}: kind {int(kd[t_, i_])} without a time (ts is NaN there; NaN marks idle entries, whose kind is <= 0)")
+      raise KalmanError(f"{who}: filter {i_}, step {t_}: time {float(tt[t_, i_])} lies before the filter's previous time {float(t_prev[t_, i_])} "
+                        "-- sort the log: a fused run does not rewind")
+    return dts, last
 
   def _run_logs_noise(self, Rs, kd, T, diag_ok=False):
     """The observation noise of run_logs() on the device -> (Rd, its NoiseMode).  Shared by the entries of every kind: the per-kind table
@@ -1965,6 +1982,85 @@ class BatchedEKF:
     if on_chunk is None:
       return xs, (self.unpack_tri(Ps) if packed else Ps)
     return None
+
+  def _has_batch_rts_pf(self):
+    return self._has_sym("batch_rts_pf")
+
+  def rts_smooth_logs(self, trace_x, trace_P, ts, kinds, t0=None, norm_quats=None, inplace=False, last_predicted=None):
+    """Batched Rauch-Tung-Striebel backward pass over the dense trace of run_logs(trace=True): N ragged logs, every filter with its own times,
+    idle entries and length, in ONE launch ({name}_batch_rts_pf; objects built with per_filter=True).
+
+    trace_x (T, N, D), trace_P (T, N, E, E): the trace; ts (T, N), kinds (T, N): as given to run_logs (NaN / kind <= 0: no entry).  t0 (N,): the
+    filters' times before the run (filter_times() as it was then); default NaN = not started, so a filter's first entry has dt = 0, the rule of
+    run_logs.  t0 only reaches the rows BEFORE a filter's first entry (below): every later dt is a difference of the log's own times.
+    Per filter the semantics are rts_smooth's (the reference's, ekf_sym.py:651-690) over the entries that stepped it -- a kind of the model,
+    whether or not the gate rejected the update.  An entry that did not step the filter (idle, or a kind the model does not have) is no predict
+    at all: the predicted pair is the filtered one and the gain is the identity, also for models whose predict(0) is not.  The recursion starts
+    at the filter's own last entry m from the PREDICTED pair of that entry (recomputed, or row i of last_predicted = (x (N, D), P (N, E, E)));
+    rows behind m, and every row of a filter without an entry, come back bit for bit.  Rows before the filter's first entry f: step f - 1 is an
+    ordinary step with that entry's dt, so it smooths the pair the filter started from, and the rows before it follow by identity steps -- the
+    reference has no counterpart for them (its estimates begin with the first observation).
+    The same refusals as run_logs: a log not in time order, a real entry without a time.  A library without the kernel
+    ({name}_has_batch_rts_pf() == 0: MSCKF models, libraries without batch_rts, and models whose per-filter instantiation does not fit the register
+    file -- of the shipped ones the dense test models rand17, rand40 and rand56) raises KalmanError: there is no other path.
+    One pass, the whole batch, full E x E covariances: multi-pass, chunks and the packed-triangle trace are smooth()'s, on a shared schedule.
+    Returns (states (T, N, D), covs (T, N, E, E)) device tensors."""
+    torch = self._torch
+    if not self.per_filter:
+      raise KalmanError("rts_smooth_logs smooths per-filter timelines: construct the orchestrator with per_filter=True")
+    if not self._has_batch_rts_pf():
+      raise KalmanError(f"lib{self.name}.so has no smoother with a schedule per filter ({self.name}_has_batch_rts_pf() == 0)")
+    N = self.batch
+    tt = self._dev(ts)
+    if tt.ndim != 2 or tt.shape[1] != N:
+      raise KalmanError(f"rts_smooth_logs: ts must be (T, N) = (T, {N}), got {tuple(tt.shape)}")
+    T = int(tt.shape[0])
+    kd = (kinds.to(device=self.device, dtype=torch.int32) if isinstance(kinds, torch.Tensor) else
+          torch.as_tensor(np.array(kinds, dtype=np.int32)).to(self.device))
+    if tuple(kd.shape) != (T, N):
+      raise KalmanError(f"rts_smooth_logs: kinds must be (T, N) = ({T}, {N}), got {tuple(kd.shape)}")
+    xf, Pf = self._dev(trace_x), self._dev(trace_P)      # (converted first: a list has no shape to refuse; a device tensor of the right kind is not copied)
+    for what, t_, shp in (("trace_x", xf, (T, N, self.dim_x)), ("trace_P", Pf, (T, N, self.dim_err, self.dim_err))):
+      if tuple(t_.shape) != shp:
+        raise KalmanError(f"rts_smooth_logs: {what} must be {shp}, got {tuple(t_.shape)}")
+    if T == 0:
+      return xf, Pf
+    ft0 = torch.full((N,), float("nan"), dtype=torch.float64, device=self.device) if t0 is None else self._dev(t0, (N,))
+    dts, _ = self._log_dts(tt, kd, ft0, "rts_smooth_logs")
+    act = torch.zeros((T, N), dtype=torch.bool, device=self.device)
+    for k in self.kinds:
+      act |= kd == int(k)
+    act = act.to(torch.uint8).contiguous()
+    xs = xf if inplace else torch.empty_like(xf)
+    Ps = Pf if inplace else torch.empty_like(Pf)
+    xl = Pl = None
+    if last_predicted is not None:
+      xl = self._dev(last_predicted[0], (N, self.dim_x))
+      Pl = self._dev(last_predicted[1], (N, self.dim_err, self.dim_err))
+    nq = self.norm_quats | ((self.norm_quats if norm_quats is None else int(bool(norm_quats))) << 1)
+    self._call("batch_rts_pf", self._p(xf), self._p(Pf), self._p(dts), self._p(act), T, self._p(self.Q), N, nq, self._p(xs), self._p(Ps),
+               self._p(xl), self._p(Pl), self._stream())
+    self._keepalive_rts = (xf, Pf, dts, act, xl, Pl)
+    return xs, Ps
+
+  def smooth_logs(self, ts, kinds, zs, Rs, norm_quats=None, flags=False):
+    """Offline estimation over N recorded logs: run_logs(trace=True) from the filters' current times, then rts_smooth_logs over that trace in
+    place.  ts, kinds, zs, Rs: as for run_logs (Rs in every form it takes); zs is NOT consumed (it is cloned, as smooth() does).  On return x / P
+    hold the FILTERED states and filter_times() is what run_logs leaves.  One pass over the whole batch with full covariances: multi-pass,
+    chunks and the packed-triangle trace are not served for per-filter logs.  Returns (xs (T, N, D), Ps (T, N, E, E), ys, flags)."""
+    torch = self._torch
+    if not self.per_filter:
+      raise KalmanError("smooth_logs smooths per-filter timelines: construct the orchestrator with per_filter=True")
+    if not self._has_batch_rts_pf():
+      raise KalmanError(f"lib{self.name}.so has no smoother with a schedule per filter ({self.name}_has_batch_rts_pf() == 0)")
+    t0 = self.filter_times().clone()
+    zc = self._dev(zs)
+    zc = zc.clone() if isinstance(zs, torch.Tensor) else zc      # run_logs consumes its observations (overwrites them with the residuals)
+    ys, tx, tP, fl = self.run_logs(ts, kinds, zc, Rs, trace=True, flags=flags)
+    if tx is None:      # T == 0
+      return tx, tP, ys, fl
+    xs, Ps = self.rts_smooth_logs(tx, tP, ts, kinds, t0=t0, norm_quats=norm_quats, inplace=True)
+    return xs, Ps, ys, fl
 
   def _rts_on(self, tx, tP, ts, m, norm_quats, packed=False):
     """In-place backward pass over a trace of m filters (m <= batch); packed: tP holds packed lower triangles (batch_rts_tri)."""

@@ -35,12 +35,19 @@ namespace rn {
 
 // Model must provide: D, E; f(x, dt, out[D]); F(x, dt, out[E*E]); err(nom, delta, out[D]);
 // inv_err(nom, tru, out[E]); normalize(x) (quaternion slices, no-op if none).
-template <class Model>
+//
+// PF = true: a schedule PER FILTER (batch_rts_pf, include/rednose_amd_filter.h RN_DECLARE_BATCH_RTS_PF) over the dense trace batch_run_pf writes.
+// `ts` is then dts (T, n), the forward dt of every entry, and `ga` (T, n) is 1 where entry (t, i) stepped filter i.  dt, `first` and the identity
+// test become values of the filter: an entry that did not step it is an identity-gain step whatever the model (no predict happened: the predicted
+// pair IS the filtered one, also where predict(0) is not the identity), the recursion starts at the filter's own last entry, and the rows behind it
+// pass through bit for bit -- the carried pair starts as the raw newest row and stays raw until that entry is met.
+template <class Model, bool PF = false>
 __global__ __launch_bounds__(64) void k_rts(const double* __restrict__ xf, const double* __restrict__ Pf,
                                             const double* __restrict__ ts, const int64_t T,
                                             const double* __restrict__ gQ, const int64_t n, const int norm_quats,
                                             double* __restrict__ xs, double* __restrict__ Ps,
-                                            const double* __restrict__ xl, const double* __restrict__ Pl) {
+                                            const double* __restrict__ xl, const double* __restrict__ Pl,
+                                            const uint8_t* __restrict__ ga = nullptr) {
   // xl / Pl (optional): the predicted pair of the last step, returned verbatim as the newest smoothed estimate (ekf_sym.py:658-659)
   constexpr int D = Model::D, E = Model::E, EE = E * E, GL = 32, FPW = 2;
   constexpr int DP = D + (D & 1);
@@ -82,9 +89,32 @@ __global__ __launch_bounds__(64) void k_rts(const double* __restrict__ xf, const
     double xn1[D];          // xk1_n: smoothed state of step k+1 (replicated per lane)
 #pragma unroll
     for (int i = 0; i < D; i++) xn1[i] = 0.0;
+    bool started = !PF;     // PF: an entry that stepped this filter lies at or behind row k + 1 (the recursion has started)
+    if constexpr (PF) {
+      copy_g2l<FPW * EE>(Pf + ((T - 1) * n + base) * EE, cnt * EE, s_N, lane);
+      copy_g2l<FPW * D>(xf + ((T - 1) * n + base) * D, cnt * D, s_x, lane);
+      wave_lds_sync();
+#pragma unroll
+      for (int i = 0; i < D; i++) xn1[i] = s_x[gg * D + i];
+      wave_lds_sync();
+    }
 
     for (int64_t k = T - 2; k >= -1; k--) {
       if (k < 0) {
+        if constexpr (PF) {
+          // a filter whose only entry is row 0: its predicted pair is known only where it was passed in (otherwise the filtered pair passes through)
+          if (!started && ga[base + gg] != 0) {
+            if (xl != nullptr) {
+#pragma unroll
+              for (int i = 0; i < D; i++) xn1[i] = xl[(base + gg) * D + i];
+            }
+            if (Pl != nullptr && on) {
+#pragma unroll
+              for (int i = 0; i < E; i++) Nn[i * E + c] = Pl[(base + gg) * EE + i * E + c];
+            }
+          }
+          wave_lds_sync();
+        }
         // the oldest smoothed state goes out un-normalised (ekf_sym.py:665-667 never reaches it)
         if (T >= 1) {
           if (c == 0 && g < cnt) {
@@ -92,7 +122,7 @@ __global__ __launch_bounds__(64) void k_rts(const double* __restrict__ xf, const
             for (int i = 0; i < D; i++) s_x[g * D + i] = xn1[i];
           }
           wave_lds_sync();
-          if (T >= 2) {
+          if (PF || T >= 2) {
             copy_l2g<FPW * D>(xs + base * D, cnt * D, s_x, lane);
             copy_l2g<FPW * EE>(Ps + base * EE, cnt * EE, s_N, lane);
           }
@@ -103,7 +133,9 @@ __global__ __launch_bounds__(64) void k_rts(const double* __restrict__ xf, const
       // ---- load the filtered pair of step k ---------------------------------------------------------
       copy_g2l<FPW * EE>(Pf + (k * n + base) * EE, cnt * EE, s_A, lane);
       copy_g2l<FPW * D>(xf + (k * n + base) * D, cnt * D, s_x, lane);
-      const double dt = ts[k + 1] - ts[k];
+      bool stepped = true;      // PF: entry k + 1 stepped this filter
+      if constexpr (PF) stepped = ga[(k + 1) * n + base + gg] != 0;
+      const double dt = PF ? (stepped ? ts[(k + 1) * n + base + gg] : 0.0) : ts[k + 1] - ts[k];
       wave_lds_sync();
       double xk[D], x1k[D];
 #pragma unroll
@@ -117,11 +149,22 @@ __global__ __launch_bounds__(64) void k_rts(const double* __restrict__ xf, const
       for (int j = 0; j < E; j++) prow[j] = (j <= cc) ? A[cc * E + j] : A[j * E + cc];
 
       // ---- recompute the predicted pair of step k+1 exactly as the forward pass did ----------------------
-      const bool first = (k == T - 2);     // recursion start: smoothed(T-1) := predicted(T-1)  (estimates[-1][0], [2])
+      const bool first = PF ? (stepped && !started) : (k == T - 2);     // recursion start: smoothed(T-1) := predicted(T-1)  (estimates[-1][0], [2]); PF: at the filter's last entry
+      if constexpr (PF) started = started || stepped;
       {
-        Model::f(xk, dt, x1k);
-        if (norm_quats & 1) Model::normalize(x1k);
-        if (c == 0 && g < cnt) Model::F(xk, dt, Fm);
+        if (PF && !stepped) {
+          // no predict happened between the two rows: xk1_k = xk_k, Fk = I (with dt = 0 the sums below give Pk1_k = the mirrored lower triangle of Pk_k)
+#pragma unroll
+          for (int i = 0; i < D; i++) x1k[i] = xk[i];
+          if (c == 0 && g < cnt) {
+#pragma unroll
+            for (int i = 0; i < EE; i++) Fm[i] = (i / E == i % E) ? 1.0 : 0.0;
+          }
+        } else {
+          Model::f(xk, dt, x1k);
+          if (norm_quats & 1) Model::normalize(x1k);
+          if (c == 0 && g < cnt) Model::F(xk, dt, Fm);
+        }
         wave_lds_sync();
         // M = Fk Pk_k^T : lane c forms column c, M[i][c] = sum_m F[i][m] Pk[c][m]; i loops stay rolled (operands in LDS)
 #pragma unroll 1
@@ -157,11 +200,11 @@ __global__ __launch_bounds__(64) void k_rts(const double* __restrict__ xf, const
         }
       }
       wave_lds_sync();
-      if (k == T - 2) {
+      if (first) {
 #pragma unroll
         for (int i = 0; i < D; i++) xn1[i] = (xl != nullptr) ? xl[(base + gg) * D + i] : x1k[i];
       }
-      if (norm_quats & 2) Model::normalize(xn1);
+      if ((norm_quats & 2) && started) Model::normalize(xn1);      // (PF: a row behind the filter's last entry leaves as it came)
       // smoothed step k+1 is final now: write it out (state after the in-place renormalisation)
       if (c == 0 && g < cnt) {
 #pragma unroll
@@ -171,15 +214,26 @@ __global__ __launch_bounds__(64) void k_rts(const double* __restrict__ xf, const
       copy_l2g<FPW * D>(xs + ((k + 1) * n + base) * D, cnt * D, s_x, lane);
       copy_l2g<FPW * EE>(Ps + ((k + 1) * n + base) * EE, cnt * EE, s_N, lane);
 
-      if (Model::ID0 && dt == 0.0 && !first) {
+      if (!first && ((PF && !stepped) || (Model::ID0 && dt == 0.0))) {
         // identity-gain step (see the head of this file): Ck = I.  Dm is symmetric by now (mirrored from its lower triangle above); the filtered
-        // covariance enters the sum as stored.  dt is a scalar of the launch: the branch is uniform.
-        double delta[E];
-        Model::inv_err(x1k, xn1, delta);
-        Model::err(xk, delta, xn1);          // xk_n, becomes xk1_n of the next (older) step
+        // covariance enters the sum as stored.  Without PF dt is a scalar of the launch (ts is shared by the batch) and the branch is uniform.
+        // With PF the test is a value of the filter and the two filters of a wavefront may part here.  That is safe for two reasons: every LDS
+        // buffer touched from here to the end of the step is the filter's own (gg), and wave_lds_sync() is a compiler fence plus
+        // __builtin_amdgcn_wave_barrier(), which emits no instruction -- the LDS serves one wavefront's accesses in issue order, so no
+        // lane waits for another inside the divergent region.  The trip count of the step loop is uniform, so the wavefront has reconverged
+        // at the loop head, where the wave-wide copy_g2l / copy_l2g stand.  A filter whose recursion has not started carries the raw pair of
+        // row k on.
+        if (started) {
+          double delta[E];
+          Model::inv_err(x1k, xn1, delta);
+          Model::err(xk, delta, xn1);          // xk_n, becomes xk1_n of the next (older) step
+        } else {
+#pragma unroll
+          for (int i = 0; i < D; i++) xn1[i] = xk[i];
+        }
         double nrow[E];
 #pragma unroll
-        for (int m = 0; m < E; m++) nrow[m] = A[cc * E + m] + Dm[cc * E + m];
+        for (int m = 0; m < E; m++) nrow[m] = started ? A[cc * E + m] + Dm[cc * E + m] : A[cc * E + m];
         wave_lds_sync();           // copy_l2g above has read s_N
         if (on) {
 #pragma unroll
@@ -281,7 +335,7 @@ __global__ __launch_bounds__(64) void k_rts(const double* __restrict__ xf, const
       wave_lds_sync();
     }
     // T == 1: nothing to smooth, the single estimate's predicted pair is not available -> copy filtered through
-    if (T == 1) {
+    if (!PF && T == 1) {
       copy_g2l<FPW * EE>(Pf + base * EE, cnt * EE, s_A, lane);
       copy_g2l<FPW * D>(xf + base * D, cnt * D, s_x, lane);
       wave_lds_sync();
@@ -507,13 +561,19 @@ __device__ unsigned long long g_rts_tl[256 * 16];
 #define RN_RTS_STAMP(i) do { } while (0)
 #endif
 
-template <class Model>
+// PF = true: a schedule per filter, the contract of k_rts<Model, true> above (ordinary models only: no MSCKF window).  The identity test is a value
+// of the filter, so the lane groups of a wavefront may disagree: a group at an identity step forms its result first, and unless every group is at
+// one the wavefront goes on through the full path -- the identity groups' lanes ride along on operands nobody reads (they would idle otherwise),
+// their state and covariance buffers are not written again, and the matrix-core products run for the other filters only.
+template <class Model, bool PF = false>
 __global__ __launch_bounds__(64, Model::WAVES) void k_rts_group(const double* __restrict__ xf, const double* __restrict__ Pf,
                                                      const double* __restrict__ ts, const int64_t T,
                                                      const double* __restrict__ gQ, const int64_t n, const int norm_quats,
                                                      double* __restrict__ xs, double* __restrict__ Ps,
-                                                     const double* __restrict__ xl, const double* __restrict__ Pl) {
+                                                     const double* __restrict__ xl, const double* __restrict__ Pl,
+                                                     const uint8_t* __restrict__ ga = nullptr) {
   constexpr int D = Model::D, E = Model::E, EE = E * E, DM = Model::DM, EM = Model::EM, MM = EM * EM;
+  static_assert(!PF || (EM == E && DM == D), "a schedule per filter: models without an MSCKF window");
   constexpr int GL = EM <= 16 ? 16 : (EM <= 32 ? 32 : 64), FPW = 64 / GL;
   constexpr int SLOT = Model::SLOT;
   constexpr int MMP = MM + (MM & 1), DP = D + (D & 1), EP = E + (E & 1), EMP = EM + (EM & 1);
@@ -570,12 +630,28 @@ __global__ __launch_bounds__(64, Model::WAVES) void k_rts_group(const double* __
       }
     }
 
+    bool started = !PF;     // PF: an entry that stepped this filter lies at or behind row k + 1 (the recursion has started)
+    if constexpr (PF) {
+      // rows behind a filter's last entry pass through: the carried pair starts as the raw newest row
+      if (on) {
+        double r0[EM];
+        rts_load_row<E, EM>(Pf + ((((T - 1) * n + fil) * EE) + (int64_t)cc * E), r0);
+#pragma unroll
+        for (int j = 0; j < EM; j++) C[c * EM + j] = r0[j];
+      }
+      if (g < cnt) { for (int i = c; i < D; i += GL) sxn[i] = xf[((T - 1) * n + fil) * D + i]; }
+      wave_lds_sync();
+    }
+
     for (int64_t k = T - 2; k >= 0; k--) {
-      const bool first = (k == T - 2);
+      bool stepped = true;      // PF: entry k + 1 stepped this filter
+      if constexpr (PF) stepped = ga[(k + 1) * n + fil] != 0;
+      const bool first = PF ? (stepped && !started) : (k == T - 2);
+      if constexpr (PF) started = started || stepped;
       // ---- A. filtered pair of step k: row c of Pk_k to registers, xk_k to LDS --------------------------------------
       const double* Pk = Pf + ((k * n + fil) * EE + (int64_t)cc * E);
       double y[EM];
-      const double dt = ts[k + 1] - ts[k];
+      const double dt = PF ? (stepped ? ts[(k + 1) * n + fil] : 0.0) : ts[k + 1] - ts[k];
       RN_RTS_STAMP(0);
       {
         // row c of Pk_k is requested first: its HBM / L2 latency passes under the scalar phase, which
@@ -586,7 +662,10 @@ __global__ __launch_bounds__(64, Model::WAVES) void k_rts_group(const double* __
         wave_lds_sync();
         // ---- B. f(xk_k), non-zeros of Fk: once per filter -> slot ----------------------------------------------------------
         RN_RTS_STAMP(1);
-        if (lead) Model::scal(sxk, dt, sl, norm_quats & 1);
+        if (lead) {
+          if (PF && !stepped) { for (int i = 0; i < D; i++) sl[Model::OFF_X + i] = sxk[i]; }      // no predict happened: xk1_k = xk_k
+          else Model::scal(sxk, dt, sl, norm_quats & 1);
+        }
         wave_lds_sync();
         RN_RTS_STAMP(2);
         // ---- C. predicted pair of step k+1 (main block): B <- Pk1_k, y <- column c of M = Fk Pk_k^T -----------------------
@@ -595,7 +674,12 @@ __global__ __launch_bounds__(64, Model::WAVES) void k_rts_group(const double* __
         // (2 EM registers for the whole kernel; beyond the immediate-offset range they cannot share a base) and spills them
         int qz = 0;
         asm volatile("" : "+v"(qz));
-        Model::mat_predict(prow, B, gQ + cc + qz, sl, cc, on, y);
+        if (PF && !stepped) {      // ... and Pk1_k = Pk_k (lower triangle mirrored)
+#pragma unroll
+          for (int j = 0; j < EM; j++) { if (on) B[c * EM + j] = prow[j]; y[j] = 0.0; }
+        } else {
+          Model::mat_predict(prow, B, gQ + cc + qz, sl, cc, on, y);
+        }
       }
       // ---- D. recursion start / difference matrix / smoothed estimate of step k+1 leaves ------------------------------------
       RN_RTS_STAMP(3);
@@ -617,7 +701,7 @@ __global__ __launch_bounds__(64, Model::WAVES) void k_rts_group(const double* __
         }
         wave_lds_sync();
       }
-      if (lead && (norm_quats & 2)) {
+      if (lead && (norm_quats & 2) && started) {      // (PF: a row behind the filter's last entry leaves as it came)
         double xn1[D];
 #pragma unroll
         for (int i = 0; i < D; i++) xn1[i] = sxn[i];
@@ -654,16 +738,23 @@ __global__ __launch_bounds__(64, Model::WAVES) void k_rts_group(const double* __
       }
 
       RN_RTS_STAMP(4);
-      if (Model::ID0 && dt == 0.0 && !first) {
+      const bool ident = !first && ((PF && !stepped) || (Model::ID0 && dt == 0.0));
+      if (ident) {
         // ---- identity-gain step (see the head of this file): Ck = I on the main block.  The difference buffer holds D = Pk1_n - Pk1_k,
-        // symmetric; the filtered row enters the sum as stored.  dt is a scalar of the launch: the branch is uniform. ----
+        // symmetric; the filtered row enters the sum as stored.  Without PF dt is a scalar of the launch and the branch is uniform.  With PF the
+        // test is a value of the filter: this body runs divergent (its buffers are the group's own; wave_lds_sync() emits no instruction),
+        // and the wavefront reconverges behind it for the ballot below.  A filter whose recursion has not started carries the raw pair of row k on. ----
         wave_lds_sync();           // the group has written xk1_n out: the buffer takes xk_n
         // (straight from / to LDS, one lane per filter: staged through register arrays like the full path's state phase, the five state-sized
         // arrays of this body put the 56-state model's one-wavefront build 53 registers over the file)
-        if (lead) Model::inv_err(sl + Model::OFF_X, sxn, sde);
+        if (lead && started) Model::inv_err(sl + Model::OFF_X, sxn, sde);
         wave_lds_sync();
         if (lead) {
-          Model::err(sxk, sde, sxn);                                               // xk_n: becomes xk1_n of the next (older) step
+          if (started) {
+            Model::err(sxk, sde, sxn);                                             // xk_n: becomes xk1_n of the next (older) step
+          } else {
+            for (int i = 0; i < D; i++) sxn[i] = sxk[i];
+          }
           if constexpr (DM < D) {
 #pragma unroll
             for (int i = DM; i < D; i++) sxn[i] = sxk[i];                          // (MSCKF: only the main states are smoothed)
@@ -676,11 +767,16 @@ __global__ __launch_bounds__(64, Model::WAVES) void k_rts_group(const double* __
 #pragma unroll
             for (int j = 0; j < 8; j++) pr[j] = (j0 + j < EM) ? Pk[j0 + j] : 0.0;
 #pragma unroll
-            for (int j = 0; j < 8; j++) { if (j0 + j < EM) C[c * EM + j0 + j] += pr[j]; }
+            for (int j = 0; j < 8; j++) { if (j0 + j < EM) C[c * EM + j0 + j] = started ? C[c * EM + j0 + j] + pr[j] : pr[j]; }
           }
         }
         wave_lds_sync();
-        continue;
+        if constexpr (!PF) continue;
+      }
+      unsigned long long fullm = ~0ull;      // PF: the lanes of the filters on the full path
+      if constexpr (PF) {
+        fullm = __ballot(!ident && g < cnt);
+        if (fullm == 0) continue;
       }
       // ---- E. Cholesky of Pk1_k, left-looking: lane c owns row c in registers; pivot row j (final since column j - 1) is
       // broadcast from LDS and every lane forms its own entry AND the pivot redundantly -- no publish / wait per column -------
@@ -780,7 +876,7 @@ __global__ __launch_bounds__(64, Model::WAVES) void k_rts_group(const double* __
       RN_RTS_STAMP(6);
       // y is column c of Ck^T, i.e. row c of Ck
       // ---- G. state: delta = Ck inv_err(xk1_k, xk1_n)[:EM]; xk_n[:DM] = err(xk_k, delta)[:DM] -----------------------------
-      if (lead) {
+      if (lead && !(PF && ident)) {
         double xb[D], xn1[D], delta[E];
 #pragma unroll
         for (int i = 0; i < D; i++) { xb[i] = sl[Model::OFF_X + i]; xn1[i] = sxn[i]; }
@@ -797,7 +893,7 @@ __global__ __launch_bounds__(64, Model::WAVES) void k_rts_group(const double* __
         if (on) sdx[c] = s0 + s1;
       }
       wave_lds_sync();
-      if (lead) {
+      if (lead && !(PF && ident)) {
         double xa[D], xnew[D], delta[E];
 #pragma unroll
         for (int i = 0; i < D; i++) xa[i] = sxk[i];
@@ -824,13 +920,28 @@ __global__ __launch_bounds__(64, Model::WAVES) void k_rts_group(const double* __
       }
       wave_lds_sync();
       RN_RTS_STAMP(8);
-      for (int fg = 0; fg < cnt; fg++)
+      for (int fg = 0; fg < cnt; fg++) {
+        if (PF && !((fullm >> (fg * GL)) & 1)) continue;      // (uniform: a filter at an identity step has its result)
         rts_products<E, EM>(s_B + fg * MMP, s_C + fg * MMP, Pf + (k * n + base + fg) * EE, lane);
+      }
       wave_lds_sync();
       RN_RTS_STAMP(9);
     }
     // ---- the oldest smoothed estimate goes out un-normalised (ekf_sym.py:665-667 never reaches it) --------------------------
-    if (T >= 2) {
+    if constexpr (PF) {
+      // a filter whose only entry is row 0: its predicted pair is known only where it was passed in (otherwise the filtered pair passes through)
+      if (!started && ga[fil] != 0) {
+        if (Pl != nullptr && on) {
+          double r0[EM];
+          rts_load_row<E, EM>(Pl + (fil * EE + (int64_t)cc * E), r0);
+#pragma unroll
+          for (int j = 0; j < EM; j++) C[c * EM + j] = r0[j];
+        }
+        if (xl != nullptr && g < cnt) { for (int i = c; i < D; i += GL) sxn[i] = xl[fil * D + i]; }
+      }
+      wave_lds_sync();
+    }
+    if (PF || T >= 2) {
       if (on) {
         double nrow[EM];
 #pragma unroll
@@ -843,7 +954,7 @@ __global__ __launch_bounds__(64, Model::WAVES) void k_rts_group(const double* __
       wave_lds_sync();
     }
     // T == 1: nothing to smooth, the single estimate's predicted pair is not available -> the filtered pair passes through
-    if (T == 1 && (!inplace_P || !inplace_x)) {
+    if (!PF && T == 1 && (!inplace_P || !inplace_x)) {
       if (!inplace_P) { for (int i = lane; i < cnt * EE; i += 64) Ps[base * EE + i] = Pf[base * EE + i]; }
       if (!inplace_x) { for (int i = lane; i < cnt * D; i += 64) xs[base * D + i] = xf[base * D + i]; }
     }

@@ -2,14 +2,17 @@
 """sha256 of `{name}.h` / `{name}.hip` as emitted (nothing compiled: no GPU, no hipcc) over models x fallbacks x tuning knobs, a line each.
 A change to the emitters that must leave every generated text as it is: run it with --tree on the parent checkout and on the branch, compare.
 
-  python tools/emit_digest.py OUT.txt [--tree OTHER_CHECKOUT] [--jobs N] [--with KNOB=V,..]
+  python tools/emit_digest.py OUT.txt [--tree OTHER_CHECKOUT] [--jobs N] [--with KNOB=V,..] [--without SUFFIX,..]
 
 --with appends knob settings to every configuration's RN_TUNE and leaves the labels as they are: a new knob whose value V is meant to reproduce a
 parent that does not know the knob is checked by comparing that file with the parent's own.  Configurations come and go with the knobs, so two
-digest files are compared by label: every line they share a label for must be the same line (`grep -Fxvf PARENT.txt BRANCH.txt` prints what is not)."""
+digest files are compared by label: every line they share a label for must be the same line (`grep -Fxvf PARENT.txt BRANCH.txt` prints what is not).
+--without takes the named functions of the C ABI ({name}_SUFFIX: prototype and definition) and the named kernels (k_...) out of the texts before
+they are hashed: a change that adds entry points or kernels and must leave everything else as it is gives, with what it adds named, the parent's own lines."""
 import argparse
 import hashlib
 import os
+import re
 import sys
 import tempfile
 from concurrent.futures import ProcessPoolExecutor
@@ -20,7 +23,9 @@ FALLBACK_MODELS = {"force_wide": ("kinematic6", "attitude"), "no_run_blk": ("kin
                    "no_rts": ("live",), "no_run": ("rand40", "feature36"),
                    "no_run_pf": ("kinematic6", "kinematic9", "live", "rand17"),
                    "no_run_pf_r": ("kinematic6", "kinematic9", "live"),
-                   "no_run_pf_rd": ("kinematic6", "kinematic9", "live", "randz10")}      # models on which the fallback changes the text
+                   "no_run_pf_rd": ("kinematic6", "kinematic9", "live", "randz10"),
+                   "no_rts4_pf": ("kinematic9", "live"),
+                   "no_rts_pf": ("kinematic6", "kinematic9", "live", "rand24")}      # models on which the fallback changes the text
 GV_MODELS = ("gv_runtime", "gv_runtime10", "gv_extra")
 LANE_GROUP_KNOBS = {      # of the lane-group family: the branches of its step kernels, the fused runs and the smoother that no default model takes
   "live": ("wide_timeline=1", "wide_lean_q=0", "wide_inline=0", "wide_db=1,wide_ft=16", "wide_lean=0,wide_lb=0,wide_db=-1,wide_ft=0", "run2_prio=3",
@@ -81,11 +86,25 @@ def example_spec(name):
     ekf_sym.emit = real
 
 
+def without(name, hdr, src, suffixes):
+  """(hdr, src) minus the C ABI functions {name}_SUFFIX: their prototypes in the header, their definitions in the source (one-line bodies
+  `sig { ... }` and bodies between the braces' own lines, the two forms emit._Abi.fn prints).  A suffix that starts with `k_` names a kernel
+  instead: its `__global__` definition goes, up to the closing brace in the first column, with the `// ----` title line in front of it."""
+  for sfx in suffixes:
+    if sfx.startswith("k_"):
+      src = re.sub(r"(?:^// ----[^\n]*\n\n?)?^__global__[^\n]*\bvoid %s\(.*?^\}\n" % sfx, "", src, flags=re.M | re.S)
+      continue
+    hdr = re.sub(r"^\w[\w ]*?\*?%s_%s\(.*?\);\n" % (name, sfx), "", hdr, flags=re.M)
+    src = re.sub(r"^\w[\w ]*?\*?%s_%s\([^\n]*\) \{(?: [^\n]* \}\n|\n.*?\n\}\n)" % (name, sfx), "", src, flags=re.M | re.S)
+  return hdr, src
+
+
 def digest(cfg):
   from rednose_amd.codegen import emit
   name, tune, fb = cfg
   os.environ["RN_TUNE"] = ",".join(t for t in (tune, os.environ.get("RN_DIGEST_WITH", "")) if t)
   hdr, src = emit.emit(gv_spec(name) if name in GV_MODELS else example_spec(name), (fb,) if fb else ())
+  hdr, src = without(name, hdr, src, [sfx for sfx in os.environ.get("RN_DIGEST_WITHOUT", "").split(",") if sfx])
   label = name + (f" RN_TUNE={tune}" if tune else "") + (f" fallback={fb}" if fb else "")
   return f"{label}: h {hashlib.sha256(hdr.encode()).hexdigest()} hip {hashlib.sha256(src.encode()).hexdigest()}"
 
@@ -96,8 +115,10 @@ if __name__ == "__main__":
   ap.add_argument("--tree", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."), help="checkout to take rednose_amd and examples from")
   ap.add_argument("--jobs", type=int, default=4)
   ap.add_argument("--with", dest="extra", default="", help="knob settings appended to every configuration's RN_TUNE (labels unchanged)")
+  ap.add_argument("--without", dest="without", default="", help="suffixes of C ABI functions taken out of the texts before hashing")
   args = ap.parse_args()
   os.environ["RN_DIGEST_WITH"] = args.extra
+  os.environ["RN_DIGEST_WITHOUT"] = args.without
   tree = os.path.abspath(args.tree)
   sys.path.insert(0, tree)
   with ProcessPoolExecutor(args.jobs, initializer=sys.path.insert, initargs=(0, tree)) as ex:
