@@ -203,8 +203,15 @@ def update_fn(spec, k, pf=False, noise=TABLE):
   feat = k.He_sym is not None
   Z = Zf - EADIM if feat else Zf
   RF, RB = lay.OFF_RF, lay.OFF_RF + EADIM * Zf
-  b = ["(void)sP;", f"double R[{Z if noise.diag else Z * Z}];"]
-  if feat:
+  # The shared table's R of a kind whose Z * Z doubles do not fit the scalar register file (2 Z^2 of its ~100 registers: Z >= 8, randz10's kind 1):
+  # `gR + row` is the same address in every lane, hipcc fetches it with scalar loads, and 162 SGPRs of R and Rl held through the update left
+  # k_run_pf on 312 of its 320 SGPR-spill lane slots with wrong results on the device (batch_rts_pf, "Found on the way").  Such a kind
+  # holds no copy: R is read through a vector address where S and the Joseph term take it, as k_run_dpf reads its Z variances.
+  lean = pf and noise is TABLE and not feat and not k.maha_test and 2 * Z * Z > 96
+  b = ["(void)sP;"] + ([] if lean else [f"double R[{Z if noise.diag else Z * Z}];"])
+  if lean:
+    b += ["int rz = 0;", 'asm volatile("" : "+v"(rz));', "const double* gRv = gR + rz;      // a vector address: R stays out of the scalar registers"]
+  elif feat:
     b += ["#pragma unroll", f"for (int i = 0; i < {Z * Z}; i++) R[i] = sl[{lay.OFF_RP} + i];      // A^T R A (phase 1)", "(void)gR;",
           f"const double rank_deficient = sl[{lay.OFF_FL}];      // 4.0 when phase 1 found Hea rank deficient"]
   elif noise.diag:
@@ -229,7 +236,7 @@ def update_fn(spec, k, pf=False, noise=TABLE):
     b.append(f"if (ok{s}) {{ " + " ".join(f"sG[{zi} * {E} + rr{s}] = kk{s}[{zi}];" for zi in range(Z)) + " }")
   b.append("rn::wave_lds_sync();")
   b += _tl(10)
-  b.append(f"double HPH[{Z * Z}], Rl[{Z if noise.diag else Z * Z}], S[{Z * Z}], L[{Z * Z}], iL[{Z}];")
+  b.append(f"double HPH[{Z * Z}], " + ("" if lean else f"Rl[{Z if noise.diag else Z * Z}], ") + f"S[{Z * Z}], L[{Z * Z}], iL[{Z}];")
   if noise.diag:      # S = HPH + diag(Rl), `scale` in front of the variances
     s_of = lambda scale: ["#pragma unroll", f"for (int i = 0; i < {Z * Z}; i++) S[i] = HPH[i];",      # noqa: E731
                           "#pragma unroll", f"for (int i = 0; i < {Z}; i++) {{ Rl[i] = {scale}[i]; S[i * {Z + 1}] += Rl[i]; }}"]
@@ -243,7 +250,8 @@ def update_fn(spec, k, pf=False, noise=TABLE):
     for zi in range(Z):
       for w in range(Z):
         b.append(f"HPH[{zi * Z + w}] = {sum_terms(term(cf, f'sG[{zi} * {E} + {j}]') for j, cf in Hs.row_nz(w))};")
-  b += (s_of("R") if noise.diag else ["#pragma unroll", f"for (int i = 0; i < {Z * Z}; i++) {{ Rl[i] = R[i]; S[i] = HPH[i] + Rl[i]; }}"]) + [
+  b += (s_of("R") if noise.diag else ["#pragma unroll", f"for (int i = 0; i < {Z * Z}; i++) S[i] = HPH[i] + gRv[i];"] if lean else
+        ["#pragma unroll", f"for (int i = 0; i < {Z * Z}; i++) {{ Rl[i] = R[i]; S[i] = HPH[i] + Rl[i]; }}"]) + [
         f"rn::spd_factor<{Z}>(S, L, iL);", "int gated = 0;"]
   if k.maha_test:
     b += ["{", f"  double v[{Z}] = {{{', '.join(f'sl[{(lay.OFF_YP if feat else lay.OFF_Y) + i}]' for i in range(Z))}}};", f"  rn::spd_forward<{Z}>(L, iL, v);",
@@ -270,7 +278,8 @@ def update_fn(spec, k, pf=False, noise=TABLE):
     b.append(f"double Dm{s}[{Z}];")
     for zi in range(Z):
       c = f"Cf{s}[{EADIM + zi}]" if feat else sum_terms(term(cf, f"row{s}[{j}]") for j, cf in Hs.row_nz(zi))
-      kr = f"kk{s}[{zi}]*Rl[{zi}]" if noise.diag else " + ".join(f"kk{s}[{w}]*Rl[{w * Z + zi}]" for w in range(Z))
+      kr = (f"kk{s}[{zi}]*Rl[{zi}]" if noise.diag else " + ".join(f"kk{s}[{w}]*gRv[{w * Z + zi}]" for w in range(Z)) if lean else
+            " + ".join(f"kk{s}[{w}]*Rl[{w * Z + zi}]" for w in range(Z)))
       b.append(f"Dm{s}[{zi}] = " + ("rank_deficient != 0.0 ? 0.0 : " if feat else "") + ("!mine ? 0.0 : " if pf else "") + f"({kr}) - ({c});")
   b.append("rn::wave_lds_sync();      // every lane has taken G (and y): the buffer takes K^T, the slot takes dx and the flags")
   fl = "(double)gated + rank_deficient" if feat else "(double)gated"

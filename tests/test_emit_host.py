@@ -147,9 +147,54 @@ def _once(build):
     return libs[key]
   return cached
 
+# What emulated LDS holds at workgroup entry (_poison_shared): the default -- the quiet-NaN pattern of tools/lds_poison.hip -- and a large finite
+# number.  A dependence on never-written LDS that a select hides from NaN (NaN compares false, the other branch is taken) shows under 1e30; the
+# fused per-filter tests run every case under both and want the same bits.
+LDS_FILLS = (("NaN", 0x7ff8dead0000beef), ("1e30", int(np.float64(1e30).view(np.uint64))))
+
+
+def set_lds_fill(lib, bits):
+  """Every workgroup the library runs from here on starts with `bits` repeated through each of its __shared__ arrays."""
+  lib.host_set_lds_fill.argtypes = [ctypes.c_uint64]
+  lib.host_set_lds_fill.restype = None
+  lib.host_set_lds_fill(bits)
+
+
+_SHARED_DECL = re.compile(r"^  __shared__ (?:__attribute__\(\(aligned\(\d+\)\)\) )?(?:unsigned )?\w+ (\w+)(?:\[[^\]\n]*\])*;[^\n]*$", re.M)
+
+
+def _poison_shared(src):
+  """Emulated LDS that starts as LDS does on the device: holding anything.  `__shared__` is `static` on the host, which starts as zeros (and, from
+  the second workgroup on, as what the one before left); a kernel that reads a word it never wrote and multiplies it by a zero coefficient gets 0
+  here and 0 * NaN there.  Behind the last `__shared__` declaration of every kernel, lane 0 fills each of the kernel's arrays with the pattern of
+  host_set_lds_fill (default: the quiet NaN of tools/lds_poison.hip) and all lanes of the workgroup meet a barrier -- before the kernel's first
+  statement that could touch LDS, which the checks below hold the text to."""
+  decls = list(_SHARED_DECL.finditer(src))
+  assert len(decls) == src.count("__shared__") - src.count("#define __shared__"), "a __shared__ declaration this transformation does not understand"
+  groups = {}
+  for m in decls:      # the kernels end at a closing brace in column 0
+    groups.setdefault(src.index("\n}\n", m.end()), []).append(m)
+  out, at = [], 0
+  for end in sorted(groups):
+    ms = groups[end]
+    names = [m.group(1) for m in ms]
+    g = src.rfind("__global__", 0, ms[0].start())
+    assert g > src.rfind("\n}\n", 0, ms[0].start()), "__shared__ outside a kernel: " + names[0]
+    head = src[g:ms[-1].end()]
+    rest = _SHARED_DECL.sub("", head)
+    assert not re.search(r"\breturn\b|wave_lds_sync|wg_barrier|\b(?:%s)\b" % "|".join(names), rest), "statements in front of the fill: " + rest[-400:]
+    out.append(src[at:ms[-1].end()])
+    out.append("\n  if (threadIdx.x == 0) { " + " ".join(f"host_lds_fill({n});" for n in names) + " }\n  host_lds_entry();")
+    at = ms[-1].end()
+  return "".join(out) + src[at:]
+
+
 def _fiberize(src):
-  """The host translation unit with its lanes as fibers (_FIBERS): <pthread.h> / <sched.h> replaced, `thread_local` variables made fiber-local."""
+  """The host translation unit with its lanes as fibers (_FIBERS): <pthread.h> / <sched.h> replaced, `thread_local` variables made fiber-local;
+  the `__shared__` arrays of its kernels poisoned at workgroup entry (_poison_shared)."""
   assert "#include <pthread.h>" in src
+  if "#define __shared__ static" in src:
+    src = _poison_shared(src)
   src = src.replace("#include <pthread.h>", _FIBERS, 1).replace("#include <sched.h>", "")
 
   def local(m):
@@ -632,6 +677,13 @@ struct Dim3 { int x; };
 static thread_local Dim3 threadIdx, blockIdx, gridDim;
 static pthread_barrier_t g_bar;
 static int g_xchg[64];
+static uint64_t g_lds_bits = 0x7ff8dead0000beefULL;      // what emulated LDS holds at workgroup entry (_poison_shared); default: the quiet NaN of tools/lds_poison.hip
+extern "C" __attribute__((visibility("default"))) void host_set_lds_fill(uint64_t bits) { g_lds_bits = bits; }
+template <class T> inline void host_lds_fill(T& a) {
+  unsigned char* p = reinterpret_cast<unsigned char*>(&a);
+  for (size_t i = 0; i < sizeof(T); i++) p[i] = (unsigned char)(g_lds_bits >> (8 * (i & 7)));
+}
+inline void host_lds_entry() { pthread_barrier_wait(&g_bar); }
 inline int __builtin_amdgcn_readlane(int v, int l) {
   g_xchg[threadIdx.x] = v;
   pthread_barrier_wait(&g_bar);
@@ -1000,6 +1052,7 @@ def _two_wave(text, nw=2):
   wavefront-wide votes / exchanges rendezvous the caller's own wavefront, rn::wg_barrier() all of them."""
   text = text.replace("static pthread_barrier_t g_bar;", "static pthread_barrier_t g_wbar[4], g_wg;").replace("struct Dim3 { int x; };\nstatic thread_local Dim3 threadIdx, blockIdx, gridDim;",
                                                                                                              "struct Dim3 { int x; };\nstatic thread_local Dim3 threadIdx, blockIdx, gridDim, blockDim;")
+  text = text.replace("inline void host_lds_entry() { pthread_barrier_wait(&g_bar); }", "inline void host_lds_entry() { pthread_barrier_wait(&g_wg); }")
   text = text.replace("pthread_barrier_wait(&g_bar)", "pthread_barrier_wait(&g_wbar[threadIdx.x >> 6])")
   text = text.replace("static int g_xchg[64];", "static int g_xchg[256];").replace("static int g_vote[64];", "static int g_vote[256];")
   text = text.replace("const int r = g_xchg[l];", "const int r = g_xchg[(threadIdx.x & ~63) + l];").replace("const int r = g_xchg[0];", "const int r = g_xchg[threadIdx.x & ~63];")

@@ -47,7 +47,9 @@ extern "C" __attribute__((visibility("default"))) void host_rts4_pf(int grid, co
   res = subprocess.run(["g++", "-O0", "-std=c++17", "-fPIC", "-shared", "-pthread", "-fno-gnu-unique", "-fvisibility=hidden", "-Wno-unknown-pragmas", "-Wno-attributes",
                         "-ffp-contract=off", str(cpp), "-o", str(lib)], capture_output=True, text=True)
   assert res.returncode == 0, res.stderr[-4000:]
-  fn = ctypes.CDLL(str(lib)).host_rts4_pf
+  dll = ctypes.CDLL(str(lib))
+  fn = dll.host_rts4_pf
+  fn.set_lds_fill = lambda bits: H.set_lds_fill(dll, bits)
   dp, bp = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_ubyte)
   fn.argtypes = [ctypes.c_int, dp, dp, dp, bp, ctypes.c_int64, dp, ctypes.c_int64, ctypes.c_int, dp, dp, dp, dp]
   return fn
@@ -93,25 +95,33 @@ def test_per_filter_register_broadcast_smoother_on_the_host(tmp_path, name):
   Q = np.ascontiguousarray(M.Q, dtype=np.float64)
   dp, bp = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_ubyte)
   ptr = lambda a: a.ctypes.data_as(dp)      # noqa: E731
+  got = {}
+  for fill_name, bits in H.LDS_FILLS:      # what LDS held at workgroup entry: the NaN pattern, then a large finite number (a select hides a NaN, not 1e30)
+    fn.set_lds_fill(bits)
+    for inplace, last in itertools.product((False, True), (False, True)):
+      bx, bP = np.full((T + 4, n, D), 7.0), np.full((T + 4, n, E, E), 7.0)
+      xs, Ps = bx[2:T + 2], bP[2:T + 2]
+      if inplace:
+        xs[:], Ps[:] = X, P
+      xf, Pf = (xs, Ps) if inplace else (X.copy(), P.copy())
+      fn(2, ptr(xf), ptr(Pf), ptr(dts), act.ctypes.data_as(bp), T, ptr(Q), n, 0, ptr(xs), ptr(Ps), ptr(xl) if last else None, ptr(Pl) if last else None)
+      what = f"{name} inplace={inplace} newest pair passed={last} (LDS starts as {fill_name})"
+      assert (bx[:2] == 7.0).all() and (bx[T + 2:] == 7.0).all() and (bP[:2] == 7.0).all() and (bP[T + 2:] == 7.0).all(), what + ": a guard row was written"
+      if not inplace:
+        assert np.array_equal(xf, X) and np.array_equal(Pf, P), what + ": the trace was written"
+      assert np.isfinite(xs).all() and np.isfinite(Ps).all(), what
+      r = restate(model, X, P, dts, act, xs, Ps, Q, x_last=xl if last else None, P_last=Pl if last else None)
+      print(f"{what}: x {r['worst']['x']:.3e} P {r['worst']['P']:.3e} pass-through rows {len(r['passed'])}")
+      assert r["bits"], what + ": a pass-through row changed"
+      assert len(r["passed"]) >= 10
+      assert r["worst"]["x"] < BOUND and r["worst"]["P"] < BOUND, (what, r["worst"])
+      if last:
+        for i in range(n):
+          st = np.nonzero(act[:, i])[0]
+          if len(st):
+            assert np.array_equal(xs[st[-1], i], xl[i]) and np.array_equal(Ps[st[-1], i], Pl[i]), (what, i)
+      got[fill_name, inplace, last] = (xs.copy(), Ps.copy())
+  fn.set_lds_fill(H.LDS_FILLS[0][1])
   for inplace, last in itertools.product((False, True), (False, True)):
-    bx, bP = np.full((T + 4, n, D), 7.0), np.full((T + 4, n, E, E), 7.0)
-    xs, Ps = bx[2:T + 2], bP[2:T + 2]
-    if inplace:
-      xs[:], Ps[:] = X, P
-    xf, Pf = (xs, Ps) if inplace else (X.copy(), P.copy())
-    fn(2, ptr(xf), ptr(Pf), ptr(dts), act.ctypes.data_as(bp), T, ptr(Q), n, 0, ptr(xs), ptr(Ps), ptr(xl) if last else None, ptr(Pl) if last else None)
-    what = f"{name} inplace={inplace} newest pair passed={last}"
-    assert (bx[:2] == 7.0).all() and (bx[T + 2:] == 7.0).all() and (bP[:2] == 7.0).all() and (bP[T + 2:] == 7.0).all(), what + ": a guard row was written"
-    if not inplace:
-      assert np.array_equal(xf, X) and np.array_equal(Pf, P), what + ": the trace was written"
-    assert np.isfinite(xs).all() and np.isfinite(Ps).all(), what
-    r = restate(model, X, P, dts, act, xs, Ps, Q, x_last=xl if last else None, P_last=Pl if last else None)
-    print(f"{what}: x {r['worst']['x']:.3e} P {r['worst']['P']:.3e} pass-through rows {len(r['passed'])}")
-    assert r["bits"], what + ": a pass-through row changed"
-    assert len(r["passed"]) >= 10
-    assert r["worst"]["x"] < BOUND and r["worst"]["P"] < BOUND, (what, r["worst"])
-    if last:
-      for i in range(n):
-        st = np.nonzero(act[:, i])[0]
-        if len(st):
-          assert np.array_equal(xs[st[-1], i], xl[i]) and np.array_equal(Ps[st[-1], i], Pl[i]), (what, i)
+    for a, b, label in zip(got["NaN", inplace, last], got["1e30", inplace, last], ("xs", "Ps")):
+      assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), f"{name} inplace={inplace} newest pair passed={last} {label}: the result depends on what LDS held at workgroup entry"

@@ -15,7 +15,7 @@ from conftest import assert_close
 from run_pf_cases import UNKNOWN, expected_flags_untouched, make_schedule, stepped_mask
 from run_pf_r_cases import entry_matrix, gates_clear, oracle_walk_r
 from run_pf_rd_cases import entry_variances, expand
-from test_emit_host import HDR, _KERNEL_PRELUDE, _RUN_GRID, _WAVE_VOTES, _WIDE_COPIES, _fiberize, _function_text, _model, _once, _wide_model
+from test_emit_host import HDR, LDS_FILLS, _KERNEL_PRELUDE, _RUN_GRID, _WAVE_VOTES, _WIDE_COPIES, _fiberize, _function_text, _model, _once, _wide_model, set_lds_fill
 from test_emit_host_kinds import _GXX, _SOLVERS, _attitude
 
 pytestmark = pytest.mark.timeout(180, method="thread")
@@ -167,51 +167,57 @@ def test_per_entry_variances_run_on_the_host(tmp_path, name, family):
   ptr = lambda a, t=dp: a.ctypes.data_as(t)      # noqa: E731
   lib.host_run_dpf.argtypes = [ctypes.c_int, ctypes.c_int, dp, dp, dp, ip, dp, ctypes.c_int64, dp, dp, ctypes.c_int64, ctypes.c_int, bp, dp, dp]
   G, got = 2, {}
-  for traced in (0, 1):
-    xg, Pg = np.full((n + 2 * G, D), 7.5), np.full((n + 2 * G, E, E), 7.5)
-    xg[G:G + n], Pg[G:G + n] = x0, P0
-    zg = np.full((T + 2, n, zmax), 777.0)
-    zg[1:T + 1] = zs
-    fg = np.full((T + 2, n), 99, dtype=np.uint8)
-    tx, tP = np.full((T + 2, n, D), 5.0), np.full((T + 2, n, E, E), 5.0)
-    Rg = Rv.copy()                                                # exactly (T, n, zmax): a read past either end is not the kernel's to make
-    lib.host_run_dpf(grid, traced, ptr(xg[G]), ptr(Pg[G]), ptr(Q), ptr(kd, ip), ptr(dts), T, ptr(zg[1]), ptr(Rg), n, int(quat_idx >= 0), ptr(fg[1], bp),
-                     ptr(tx[1]) if traced else None, ptr(tP[1]) if traced else None)
-    what = f"{name} {'k_run_dpf traced' if traced else 'k_run_dpf'}"
-    assert np.array_equal(Rg, Rv, equal_nan=True), what + ": R is read only"
-    for a in (xg, Pg, zg, tx, tP):
-      assert not np.isnan(a).any(), what + ": NaN in an output (an unused row of R has reached it)"
-    for a, fill in ((xg, 7.5), (Pg, 7.5)):
-      assert (a[:G] == fill).all() and (a[-G:] == fill).all(), what + ": guard filters"
-    for a, fill in ((zg, 777.0), (fg, 99), (tx, 5.0), (tP, 5.0)):
-      assert (a[0] == fill).all() and (a[T + 1] == fill).all(), what + ": guard rows"
-    if not traced:
-      assert (tx == 5.0).all() and (tP == 5.0).all()
-    xh, Ph, zh, fl = xg[G:G + n], Pg[G:G + n], zg[1:T + 1], fg[1:T + 1]
-    assert np.array_equal(fl, fr), what + ": flags (16 idle, 8 unknown kind, the gate bit of stepped entries)"
-    assert np.array_equal(zh[~on], zs[~on]), what + ": z rows of idle entries pass through bit for bit"
-    nv = info["never"]
-    assert np.array_equal(xh[nv], x0[nv]) and np.array_equal(Ph[nv], P0[nv]), what + ": the never-stepped filter is not written back"
-    for g_, w_, label in ((xh, xr, "x"), (Ph.reshape(n, -1), Pr.reshape(n, -1), "P")):
-      err = np.abs(np.delete(g_, nv, 0) - np.delete(w_, nv, 0)) / np.abs(np.delete(w_, nv, 0)).max(axis=1, keepdims=True)
-      assert err.max() <= tol, f"{what} {label}: {err.max():.3e} of the row maximum (bound {tol:.0e})"
-    for k in spec.kinds:
-      Z = k.zdim
-      m = kd == k.kind
-      assert_close(zh[m][:, :Z], zr[m][:, :Z], rtol=tol, atol=tol * 1e-2 * max(1.0, np.abs(zs).max()), what=what + f" kind {k.kind} y")
-      assert np.array_equal(zh[m][:, Z:], zs[m][:, Z:]), what + f" kind {k.kind}: z columns beyond Z"
-    if traced:
-      for g_, w_, label in ((tx[1:T + 1].reshape(T * n, -1), txr.reshape(T * n, -1), "trace x"), (tP[1:T + 1].reshape(T * n, -1), tPr.reshape(T * n, -1), "trace P")):
-        err = np.abs(g_ - w_) / np.abs(w_).max(axis=1, keepdims=True)
+  for fill_name, bits in LDS_FILLS:      # what LDS held at workgroup entry: the NaN pattern, then a large finite number (a select hides a NaN, not 1e30)
+    set_lds_fill(lib, bits)
+    for traced in (0, 1):
+      xg, Pg = np.full((n + 2 * G, D), 7.5), np.full((n + 2 * G, E, E), 7.5)
+      xg[G:G + n], Pg[G:G + n] = x0, P0
+      zg = np.full((T + 2, n, zmax), 777.0)
+      zg[1:T + 1] = zs
+      fg = np.full((T + 2, n), 99, dtype=np.uint8)
+      tx, tP = np.full((T + 2, n, D), 5.0), np.full((T + 2, n, E, E), 5.0)
+      Rg = Rv.copy()                                                # exactly (T, n, zmax): a read past either end is not the kernel's to make
+      lib.host_run_dpf(grid, traced, ptr(xg[G]), ptr(Pg[G]), ptr(Q), ptr(kd, ip), ptr(dts), T, ptr(zg[1]), ptr(Rg), n, int(quat_idx >= 0), ptr(fg[1], bp),
+                       ptr(tx[1]) if traced else None, ptr(tP[1]) if traced else None)
+      what = f"{name} {'k_run_dpf traced' if traced else 'k_run_dpf'} (LDS starts as {fill_name})"
+      assert np.array_equal(Rg, Rv, equal_nan=True), what + ": R is read only"
+      for a in (xg, Pg, zg, tx, tP):
+        assert not np.isnan(a).any(), what + ": NaN in an output (an unused row of R has reached it)"
+      for a, fill in ((xg, 7.5), (Pg, 7.5)):
+        assert (a[:G] == fill).all() and (a[-G:] == fill).all(), what + ": guard filters"
+      for a, fill in ((zg, 777.0), (fg, 99), (tx, 5.0), (tP, 5.0)):
+        assert (a[0] == fill).all() and (a[T + 1] == fill).all(), what + ": guard rows"
+      if not traced:
+        assert (tx == 5.0).all() and (tP == 5.0).all()
+      xh, Ph, zh, fl = xg[G:G + n], Pg[G:G + n], zg[1:T + 1], fg[1:T + 1]
+      assert np.array_equal(fl, fr), what + ": flags (16 idle, 8 unknown kind, the gate bit of stepped entries)"
+      assert np.array_equal(zh[~on], zs[~on]), what + ": z rows of idle entries pass through bit for bit"
+      nv = info["never"]
+      assert np.array_equal(xh[nv], x0[nv]) and np.array_equal(Ph[nv], P0[nv]), what + ": the never-stepped filter is not written back"
+      for g_, w_, label in ((xh, xr, "x"), (Ph.reshape(n, -1), Pr.reshape(n, -1), "P")):
+        err = np.abs(np.delete(g_, nv, 0) - np.delete(w_, nv, 0)) / np.abs(np.delete(w_, nv, 0)).max(axis=1, keepdims=True)
         assert err.max() <= tol, f"{what} {label}: {err.max():.3e} of the row maximum (bound {tol:.0e})"
-      live = np.ones(n, dtype=bool)
-      live[nv] = False
-      assert np.array_equal(tx[T][live], xh[live]) and np.array_equal(tP[T][live], Ph[live]), what + ": last trace row"
-      # dense trace: an idle entry's row repeats the row before it
-      idle = ~on[1:]
-      assert np.array_equal(tx[2:T + 1][idle], tx[1:T][idle]) and np.array_equal(tP[2:T + 1][idle], tP[1:T][idle]), what + ": trace rows of idle entries"
-    got[traced] = (xh.copy(), Ph.copy(), zh.copy(), fl.copy())
-  for a, b in zip(got[0], got[1]):
+      for k in spec.kinds:
+        Z = k.zdim
+        m = kd == k.kind
+        assert_close(zh[m][:, :Z], zr[m][:, :Z], rtol=tol, atol=tol * 1e-2 * max(1.0, np.abs(zs).max()), what=what + f" kind {k.kind} y")
+        assert np.array_equal(zh[m][:, Z:], zs[m][:, Z:]), what + f" kind {k.kind}: z columns beyond Z"
+      if traced:
+        for g_, w_, label in ((tx[1:T + 1].reshape(T * n, -1), txr.reshape(T * n, -1), "trace x"), (tP[1:T + 1].reshape(T * n, -1), tPr.reshape(T * n, -1), "trace P")):
+          err = np.abs(g_ - w_) / np.abs(w_).max(axis=1, keepdims=True)
+          assert err.max() <= tol, f"{what} {label}: {err.max():.3e} of the row maximum (bound {tol:.0e})"
+        live = np.ones(n, dtype=bool)
+        live[nv] = False
+        assert np.array_equal(tx[T][live], xh[live]) and np.array_equal(tP[T][live], Ph[live]), what + ": last trace row"
+        # dense trace: an idle entry's row repeats the row before it
+        idle = ~on[1:]
+        assert np.array_equal(tx[2:T + 1][idle], tx[1:T][idle]) and np.array_equal(tP[2:T + 1][idle], tP[1:T][idle]), what + ": trace rows of idle entries"
+      got[fill_name, traced] = (xh.copy(), Ph.copy(), zh.copy(), fl.copy(), tx.copy(), tP.copy())
+  set_lds_fill(lib, LDS_FILLS[0][1])
+  for a, b in zip(got["NaN", 0][:4], got["NaN", 1][:4]):
     assert np.array_equal(a, b), f"{name}: traced and untraced kernels differ"
+  for traced in (0, 1):
+    for a, b, label in zip(got["NaN", traced], got["1e30", traced], ("x", "P", "y", "flags", "trace x", "trace P")):
+      assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), f"{name} traced={traced} {label}: the result depends on what LDS held at workgroup entry"
   if not any(k.maha_test for k in spec.kinds):
     assert not (fr[on] & 1).any()

@@ -120,9 +120,7 @@ def _trace(name, n, T, seed, t0=0.9):
   sch = schedule(n, T, kinds, seed=seed)
   zs = _observations(name, rng, sch["kinds"], hx)
   f.init_state(x0, P0, np.full(n, t0))
-  # (randz10: its trace is taken from the step walk.  Its fused k_run_pf gave a different trace on identical calls under this schedule -- sums
-  # differing from the tenth digit on, NaN on some calls -- which is not the smoother's to answer for: every smoother call on one trace agreed.)
-  _, tx, tP, _ = f.run_logs(sch["ts_fwd"], sch["kinds"], zs, Rs, trace=True, exact=(name == "randz10"))
+  _, tx, tP, _ = f.run_logs(sch["ts_fwd"], sch["kinds"], zs, Rs, trace=True)
   dts = forward_dts(sch["ts"], sch["kinds_rts"], np.full(n, t0))
   act = np.isin(sch["kinds_rts"], np.array(kinds)).astype(np.uint8)
   assert np.array_equal(dts * act, forward_dts(sch["ts_fwd"], sch["kinds"], np.full(n, t0)) * act)      # the unknown-kind entry moves no dt

@@ -1,11 +1,19 @@
 """The fused run with a schedule per filter ({name}_batch_run_pf, BatchedEKF.run_logs): N logs replayed in one launch, against the step
 walk it replaces (one batch_predict_update_kinds launch per step on a copy of the state), against batch_run on a shared schedule, against
 the oracle stepping each filter through its own entries, and on the reference's logs (tests/golden/perfilter_timelines.npz), each sorted
-by time.  Both kernel families: lane per filter (kinematic6, attitude) and lane group (kinematic9, live)."""
+by time.  Both kernel families: lane per filter (kinematic6, attitude) and lane group (kinematic9, live).  At the end of the file: the lane-group
+kernels of randz10, randaff11, rand24 and rand8 on the ragged logs of tests/rts_pf_cases.py -- parity with the step walk and the oracle, the same bits
+whatever LDS held before the call, randz10's shared table against its per-entry variances; measured maxima in profiles/run_pf_parity.json (written
+under RN_WRITE_PARITY=1; the committed file is such a run's; every figure is a fraction of the tolerance it is held to)."""
+import ctypes
+import json
+import os
+import re
+
 import numpy as np
 import pytest
 
-from conftest import assert_close, golden
+from conftest import REPO, assert_close, golden
 from run_pf_cases import expected_flags_untouched, make_schedule, oracle_walk, r_table, stepped_mask
 from test_gpu_kinds import _case as _kinds_case
 
@@ -15,6 +23,16 @@ SMALL = ("kinematic6", "attitude")
 
 
 def _case(name):
+  if name.startswith(("randaff", "randz")):      # (the seeded random filters tests/test_gpu_kinds.py does not look up)
+    from examples import model_class_of
+    R_ = model_class_of(name)
+    Dr = int(R_.dim)
+
+    def rstates(rng, n):
+      x0 = R_.initial_x[None] + rng.normal(size=(n, Dr)) * 0.3
+      A = rng.normal(size=(n, Dr, Dr)) * 0.2
+      return x0, np.diag(R_.initial_P_diag)[None] + A @ A.transpose(0, 2, 1), None
+    return R_, dict(dim=(Dr, Dr), quat=[]), -1, tuple(sorted(R_.obs_noise)), {k: np.atleast_2d(R_.obs_noise[k]) for k in R_.obs_noise}, rstates
   if name != "kinematic6":
     return _kinds_case(name)
   from examples.kinematic6_kf import Kinematic6Kalman as M
@@ -347,3 +365,212 @@ def test_run_logs_plumbing():
   assert_close(res[0][0], res[1][0], rtol=xb[0], floor=xb[1], what="state after the call behind the run")
   assert_close(res[0][1].reshape(n, -1), res[1][1].reshape(n, -1), rtol=Pb[0], floor=Pb[1], what="covariance after the call behind the run")
   assert np.array_equal(res[0][2], res[1][2])
+
+
+# ---- the lane-group kernels no other test launches: randz10 (a 9-dimensional kind: 81-entry R / HPH / S / L per lane, two observation entries per
+# lane), randaff11 (affine: predict(0) is not the identity), rand24 (16 lanes per filter), rand8 -- on the logs of tests/rts_pf_cases.schedule:
+# filters without an entry, with a single one, late starts, early ends, about a third of the dts exactly 0 ------------------------------------------
+
+WIDE_PF = ["randz10", "randaff11", "rand24", "rand8"]
+T_LOG, T0_LOG = 9, 0.9
+ORACLE_BOUND = (1e-11, 1e-13)      # test_against_the_oracle's (rtol, floor), x and P alike
+_PARITY = {}
+
+
+def _record(key, **figures):
+  """The measured maxima, as fractions of the tolerance they are held to (assert_close's rtol |want| + floor max|row|): below 1 means within bounds."""
+  _PARITY[key] = {k: float(v) for k, v in figures.items()}
+  if os.environ.get("RN_WRITE_PARITY"):
+    fn = os.path.join(REPO, "profiles", "run_pf_parity.json")
+    old = {}
+    if os.path.exists(fn):
+      with open(fn, encoding="utf-8") as f:
+        old = json.load(f)
+    old.update(_PARITY)
+    with open(fn, "w", encoding="utf-8") as f:
+      json.dump(old, f, indent=1, sort_keys=True)
+      f.write("\n")
+
+
+def _of_tol(got, want, rtol, floor, atol=0.0):
+  """max |got - want| / (assert_close's tolerance)"""
+  got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+  if got.size == 0:
+    return 0.0
+  tol = rtol * np.abs(want) + floor * np.max(np.abs(want), axis=-1, keepdims=True) + atol + 1e-300
+  return float(np.max(np.abs(got - want) / tol))
+
+
+def _fpw_wide(name):
+  """Filters per wavefront of the lane-group fused run, as the generated text states it."""
+  from examples import GENERATED_DIR, ensure_generated
+  ensure_generated([name])
+  with open(os.path.join(GENERATED_DIR, f"{name}.hip"), encoding="utf-8") as fh:
+    return int(re.search(r"constexpr int FPWR = (\d+);", fh.read()).group(1))
+
+
+def _lds():
+  """tools/liblds_poison.so (lds_poison: the NaN pattern conftest fills LDS with; lds_fill: any 64-bit pattern), None where it is not built."""
+  fn = os.path.join(REPO, "tools", "liblds_poison.so")
+  if not os.path.exists(fn):
+    return None
+  lib = ctypes.CDLL(fn)
+  lib.lds_poison.argtypes, lib.lds_poison.restype = [ctypes.c_void_p], None
+  lib.lds_fill.argtypes, lib.lds_fill.restype = [ctypes.c_uint64, ctypes.c_void_p], None
+  return lib
+
+
+_LOGS = {}
+
+
+def _log_inputs(name, n, T=T_LOG, seed=3):
+  """One seeded case per (model, n), shared by the tests below (which copy what a call consumes): states with a symmetric P0, the ragged logs, observations."""
+  from rts_pf_cases import forward_dts, schedule
+  if (name, n, T) not in _LOGS:
+    M, kw, qi, kinds, Rs, states = _case(name)
+    rng = np.random.default_rng(seed)
+    x0, P0, hx = states(rng, n)
+    P0 = 0.5 * (P0 + P0.transpose(0, 2, 1))
+    sch = schedule(n, T, kinds, seed=seed)
+    kd = sch["kinds"]
+    zmax = max(R.shape[0] for R in Rs.values())
+    zs = rng.normal(size=(T, n, zmax)) * 0.5
+    if hx is not None:      # observations near h(x) of the state the filter starts from
+      for k in kinds:
+        Z = Rs[k].shape[0]
+        tt_, ii_ = np.nonzero(kd == k)
+        zs[tt_, ii_, :Z] = hx[k][ii_] + rng.normal(size=(tt_.size, Z)) * np.sqrt(np.diag(Rs[k]))
+    dts = forward_dts(sch["ts_fwd"], kd, np.full(n, T0_LOG))
+    on = stepped_mask(kd, kinds)
+    assert np.array_equal(on, kd > 0)
+    if n >= 7:
+      assert (~on.any(axis=0)).any() and (on.sum(axis=0) == 1).any() and (dts[on] == 0.0).any() and (dts[on] > 0.0).any()
+    _LOGS[name, n, T] = dict(M=M, qi=qi, kinds=kinds, Rs=Rs, x0=x0, P0=P0, ts=sch["ts_fwd"], kd=kd, zs=zs, dts=dts, on=on)
+  return _LOGS[name, n, T]
+
+
+def _replay(f, c, Rs=None, exact=False):
+  """run_logs(trace=True, flags=True) from the case's start -> ((x, P, y, flags, trace_x, trace_P) as numpy arrays, the entry points launched)"""
+  import torch
+  n = c["x0"].shape[0]
+  f.init_state(c["x0"], c["P0"], np.full(n, T0_LOG))
+  real, seen = f._call, []
+
+  def spy(sym, *args):
+    seen.append(sym)
+    return real(sym, *args)
+  f._call = spy
+  y, tx, tP, fl = f.run_logs(c["ts"], c["kd"], c["zs"].copy(), c["Rs"] if Rs is None else Rs, trace=True, flags=True, exact=exact)
+  torch.cuda.synchronize()
+  del f._call
+  return (f.state(), f.covs(), y.cpu().numpy(), fl.cpu().numpy(), tx.cpu().numpy(), tP.cpu().numpy()), seen
+
+
+@pytest.mark.parametrize("n_case", ["1", "FPW+1", "130"])
+@pytest.mark.parametrize("name", WIDE_PF)
+def test_lane_group_logs_against_the_step_walk_and_the_oracle(name, n_case):
+  """One batch_run_pf launch against run_logs(exact=True) on a second object at test_shapes_against_the_step_walk's lane-group bounds, and
+  against the oracle stepping at most 16 filters (the first two tiles' worth and the ragged end) through their own entries at
+  test_against_the_oracle's.  Flags equal; idle rows of y and the filters without an entry bit for bit."""
+  from oracle_lib import OracleLib
+  n = {"1": 1, "FPW+1": _fpw_wide(name) + 1, "130": 130}[n_case]
+  c = _log_inputs(name, n)
+  T, kd, on, zs, Rs, kinds = T_LOG, c["kd"], c["on"], c["zs"], c["Rs"], c["kinds"]
+  f, g = _filter(name, n)[0], _filter(name, n)[0]
+  assert f._has_batch_run_pf()
+  got, seen = _replay(f, c)
+  assert seen == ["batch_run_pf"], seen
+  want, walked = _replay(g, c, exact=True)
+  assert "batch_run_pf" not in walked and len(walked) >= T
+  what = f"{name} n={n} T={T}"
+  for a in got:
+    assert np.isfinite(a.astype(np.float64)).all(), what + ": an output is not finite"
+  never = ~on.any(axis=0)
+  assert np.array_equal(got[0][never], c["x0"][never]) and np.array_equal(got[1][never], c["P0"][never]), what + ": filters without an entry, bit for bit"
+  assert np.array_equal(got[3][~on], expected_flags_untouched(kd, kinds)[~on]), what + ": 16 at idle entries"
+  (xb, Pb) = _bounds(name)
+  fig = dict(x_walk=_of_tol(got[0], want[0], *xb), P_walk=_of_tol(got[1].reshape(n, -1), want[1].reshape(n, -1), *Pb),
+             trace_x_walk=_of_tol(got[4].reshape(T * n, -1), want[4].reshape(T * n, -1), *xb),
+             trace_P_walk=_of_tol(got[5].reshape(T * n, -1), want[5].reshape(T * n, -1), *Pb))
+  # the oracle on a subset
+  sub = np.unique(np.r_[np.arange(min(n, 8)), np.arange(max(0, n - 8), n)])
+  assert sub.size <= 16
+  m = sub.size
+  xo, Po, zo = c["x0"][sub].copy(), c["P0"][sub].copy(), np.ascontiguousarray(zs[:, sub])
+  fr, txr, tPr = oracle_walk(OracleLib(name), {k: Rs[k].shape[0] for k in kinds}, Rs, np.asarray(c["M"].Q, dtype=np.float64), np.ascontiguousarray(kd[:, sub]),
+                             np.ascontiguousarray(c["dts"][:, sub]), xo, Po, zo, quat_idx=c["qi"], trace=True)
+  ro, fo = ORACLE_BOUND
+  fig.update(x_oracle=_of_tol(got[0][sub], xo, ro, fo), P_oracle=_of_tol(got[1][sub].reshape(m, -1), Po.reshape(m, -1), ro, fo),
+             trace_x_oracle=_of_tol(got[4][:, sub].reshape(T * m, -1), txr.reshape(T * m, -1), ro, fo),
+             trace_P_oracle=_of_tol(got[5][:, sub].reshape(T * m, -1), tPr.reshape(T * m, -1), ro, fo))
+  Y = got[2][:, sub]
+  fig["y_oracle"] = max([_of_tol(Y[kd[:, sub] == k][:, :Rs[k].shape[0]], zo[kd[:, sub] == k][:, :Rs[k].shape[0]], ro, 0.0, atol=fo * max(1.0, np.abs(zs).max()))
+                         for k in kinds])
+  print(what, {k: f"{v:.3e}" for k, v in fig.items()}, "(fractions of the tolerance)")
+  _record(f"parity/{name}/n={n}", **fig)
+  _compare(name, what + " vs the step walk", got, want, on, zs, Rs, kd, True)
+  live = ~never
+  assert np.array_equal(got[4][-1][live], got[0][live]) and np.array_equal(got[5][-1][live], got[1][live]), what + ": last trace row"
+  assert np.array_equal(got[3][:, sub], fr), what + ": flags vs the oracle"
+  assert_close(got[0][sub], xo, rtol=ro, floor=fo, what=what + " vs oracle x")
+  assert_close(got[1][sub].reshape(m, -1), Po.reshape(m, -1), rtol=ro, floor=fo, what=what + " vs oracle P")
+  for k in kinds:
+    Z, sel = Rs[k].shape[0], kd[:, sub] == k
+    if sel.any():
+      assert_close(Y[sel][:, :Z], zo[sel][:, :Z], rtol=ro, atol=fo * max(1.0, np.abs(zs).max()), what=what + f" vs oracle y kind {k}")
+  assert_close(got[4][:, sub].reshape(T * m, -1), txr.reshape(T * m, -1), rtol=ro, floor=fo, what=what + " vs oracle trace x")
+  assert_close(got[5][:, sub].reshape(T * m, -1), tPr.reshape(T * m, -1), rtol=ro, floor=fo, what=what + " vs oracle trace P")
+
+
+@pytest.mark.parametrize("name", WIDE_PF + ["kinematic9", "live"])
+def test_same_call_same_bits_whatever_lds_held(name):
+  """Three calls on identical inputs from a re-initialised object: behind the NaN pattern of lds_poison, behind lds_fill(1e30) and behind
+  lds_fill(-0.0).  Every output finite and the same bits in all three: nothing the kernel computes comes from LDS (or a register) it did not write.
+  A comparison of values -- three calls, no loop."""
+  import torch
+  n = 130
+  c = _log_inputs(name, n)
+  f = _filter(name, n)[0]
+  assert f._has_batch_run_pf()
+  lds = _lds()
+  bits = lambda v: int(np.float64(v).view(np.uint64))      # noqa: E731
+  out = []
+  for label, refill in (("lds_poison", lambda: lds.lds_poison(None)), ("lds_fill(1e30)", lambda: lds.lds_fill(bits(1e30), None)),
+                        ("lds_fill(-0.0)", lambda: lds.lds_fill(bits(-0.0), None))):
+    if lds is not None:
+      refill()
+      torch.cuda.synchronize()
+    got, seen = _replay(f, c)
+    assert seen == ["batch_run_pf"], (label, seen)
+    out.append((label, got))
+  names = ("x", "P", "y", "flags", "trace_x", "trace_P")
+  for label, got in out:
+    for a, nm in zip(got, names):
+      assert np.isfinite(a.astype(np.float64)).all(), f"{name} behind {label}: {nm} is not finite ({int((~np.isfinite(a.astype(np.float64))).sum())} entries)"
+  for label, got in out[1:]:
+    for a, b, nm in zip(out[0][1], got, names):
+      diff = (a.view(np.uint64) != b.view(np.uint64)) if a.dtype == np.float64 else (a != b)
+      assert not diff.any(), f"{name}: {nm} behind {label} differs from the call behind {out[0][0]} in {int(diff.sum())} of {diff.size} entries"
+
+
+def test_randz10_shared_table_against_per_entry_variances():
+  """The same log through batch_run_pf (the shared diagonal table) and through batch_run_pf_rd (the same variances per entry), at the bounds
+  tests/test_gpu_run_pf_rd.py::test_against_batch_run_pf_r_on_the_expanded_rows holds two flavours to (the lane-per-filter ones, equal flags).
+  With the parity test above: a defect of the TABLE flavour's compiled code fails here and there, one of the shared structure fails there only."""
+  name, n = "randz10", 130
+  c = _log_inputs(name, n)
+  T, kd, on, Rs = T_LOG, c["kd"], c["on"], c["Rs"]
+  f, g = _filter(name, n)[0], _filter(name, n)[0]
+  assert f._has_batch_run_pf() and g._has_batch_run_pf_rd()
+  for R in Rs.values():
+    assert not (R - np.diag(np.diag(R))).any()
+  Rv = {k: np.ascontiguousarray(np.broadcast_to(np.diag(Rs[k]), (T, n, Rs[k].shape[0]))) for k in Rs}
+  tab, seen_t = _replay(f, c)
+  var, seen_v = _replay(g, c, Rs=Rv)
+  assert seen_t == ["batch_run_pf"] and seen_v == ["batch_run_pf_rd"], (seen_t, seen_v)
+  assert np.array_equal(tab[3], var[3]), "flags"
+  (xb, Pb) = _bounds("kinematic6")
+  _record(f"flavours/{name}/n={n}", x=_of_tol(tab[0], var[0], *xb), P=_of_tol(tab[1].reshape(n, -1), var[1].reshape(n, -1), *Pb),
+          trace_x=_of_tol(tab[4].reshape(T * n, -1), var[4].reshape(T * n, -1), *xb), trace_P=_of_tol(tab[5].reshape(T * n, -1), var[5].reshape(T * n, -1), *Pb))
+  print(name, "table vs variances", _PARITY[f"flavours/{name}/n={n}"])
+  _compare("kinematic6", f"{name} table vs variances per entry", tab, var, on, c["zs"], Rs, kd, True)
