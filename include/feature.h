@@ -46,6 +46,7 @@ int feature_batch_rewind_fetch(const int32_t *rep_slot, const int32_t *rep_n, in
 int feature_batch_maha_1(const double *x, const double *P, const double *z, const double *R, int r_per_filter, const double *ea, int64_t n, double *d2, void *stream);
 int feature_batch_maha_2(const double *x, const double *P, const double *z, const double *R, int r_per_filter, const double *ea, int64_t n, double *d2, void *stream);
 int feature_batch_augment(double *x, double *P, int64_t n, void *stream);
+int feature_batch_augment_masked(double *x, double *P, const uint8_t *active, int64_t n, void *stream);
 void feature_msckf_dims(int *dims);
 int feature_kind_eadim(int kind);
 int feature_zmax(void);
@@ -59,6 +60,8 @@ int feature_has_batch_run_pf_r(void);
 int feature_batch_run_pf_r(double *x, double *P, const double *Q, const int32_t *kinds, const double *dts, int64_t T, double *z, const double *R, int64_t n, int norm_quats, uint8_t *flags, double *trace_x, double *trace_P, void *stream);
 int feature_has_batch_run_pf_rd(void);
 int feature_batch_run_pf_rd(double *x, double *P, const double *Q, const int32_t *kinds, const double *dts, int64_t T, double *z, const double *R, int64_t n, int norm_quats, uint8_t *flags, double *trace_x, double *trace_P, void *stream);
+int feature_has_batch_run_pf_ea(void);
+int feature_batch_run_pf_ea(double *x, double *P, const double *Q, const int32_t *kinds, const double *dts, int64_t T, double *z, const double *R, int64_t n, int norm_quats, uint8_t *flags, double *trace_x, double *trace_P, const double *ea, const int32_t *augment, void *stream);
 int feature_has_tri_trace(void);
 int feature_batch_rts(const double *xf, const double *Pf, const double *ts, int64_t T, const double *Q, int64_t n, int norm_quats, double *xs, double *Ps, const double *x_last, const double *P_last, void *stream);
 int feature_has_batch_rts_pf(void);

@@ -65,6 +65,8 @@ int kinematic9_has_batch_run_pf_r(void);
 int kinematic9_batch_run_pf_r(double *x, double *P, const double *Q, const int32_t *kinds, const double *dts, int64_t T, double *z, const double *R, int64_t n, int norm_quats, uint8_t *flags, double *trace_x, double *trace_P, void *stream);
 int kinematic9_has_batch_run_pf_rd(void);
 int kinematic9_batch_run_pf_rd(double *x, double *P, const double *Q, const int32_t *kinds, const double *dts, int64_t T, double *z, const double *R, int64_t n, int norm_quats, uint8_t *flags, double *trace_x, double *trace_P, void *stream);
+int kinematic9_has_batch_run_pf_ea(void);
+int kinematic9_batch_run_pf_ea(double *x, double *P, const double *Q, const int32_t *kinds, const double *dts, int64_t T, double *z, const double *R, int64_t n, int norm_quats, uint8_t *flags, double *trace_x, double *trace_P, const double *ea, const int32_t *augment, void *stream);
 int kinematic9_has_tri_trace(void);
 int kinematic9_batch_rts(const double *xf, const double *Pf, const double *ts, int64_t T, const double *Q, int64_t n, int norm_quats, double *xs, double *Ps, const double *x_last, const double *P_last, void *stream);
 int kinematic9_has_batch_rts_pf(void);

@@ -383,6 +383,31 @@ extern "C" {
                                    int64_t T, double *z, const double *R, int64_t n, int norm_quats,               \
                                    uint8_t *flags, double *trace_x, double *trace_P, void *stream);
 
+/* THE SAME RUN FOR MSCKF MODELS: extra arguments per entry (a feature track's landmark) and a window shift per filter.  N camera logs,
+ * each with its own feature tracks and its own keyframe times, in one launch.
+ *   {name}_has_batch_run_pf_ea() == 1: the library has the kernel (MSCKF models with a fused run).  0: every other library --
+ *   batch_run_pf_ea then returns status 4 and nothing is launched (batch_run_pf serves the models without a window; walk the schedule
+ *   with batch_predict_update_{k}_masked and batch_augment_masked otherwise).  has_batch_run_pf() stays 0 for MSCKF models.
+ * x .. trace_P are batch_run_pf's arguments (R: one row of zmax * zmax doubles per kind), and so are the status codes, the argument checks
+ * (NULL -> 2, `ea` included; misaligned -> 3, T == 0 or n == 0 a no-op that returns 0, no device -> 1), the flag rules 16 / 8, the dense
+ * trace, (P + P^T) / 2 at entry, "a filter that no entry stepped is not written back", and z: rows of idle entries and the columns beyond
+ * Z pass through; a feature-track kind writes Z - 3 residual rows in the reference's basis (above), as batch_run does.
+ *   ea is a DEVICE array (T, n, EA), EA the largest {name}_kind_eadim: the leading doubles of row (t, i) are the extra arguments of entry
+ *   (t, i).  Only the rows of entries whose kind takes extra arguments are read; the others may hold anything, NaN included.
+ *   augment is a DEVICE array (T, n) of int32, or NULL (no shifts): augment[t, i] != 0 shifts the window of filter i (batch_augment) after
+ *   its entry t.  Ignored at entries that did not step the filter (idle, unknown kind).  An entry whose null-space projection was rank
+ *   deficient (flag 4: the measurement is ignored) still shifts, as in batch_run.  trace row (t, i) is the estimate BEFORE that shift.
+ * The step-granular half, exported beside batch_augment by MSCKF libraries only (no macro of its own, like nothing else here that
+ * only some libraries have apart from RN_DECLARE_BATCH_MSCKF):
+ *   int {name}_batch_augment_masked(double *x, double *P, const uint8_t *active, int64_t n, void *stream);
+ * batch_augment on the filters with active[i] != 0, the others untouched bit for bit; active == NULL: every filter. */
+#define RN_DECLARE_BATCH_RUN_PF_EA(name)                                                                          \
+  int RN_FN(name, has_batch_run_pf_ea)(void);                                                                     \
+  int RN_FN(name, batch_run_pf_ea)(double *x, double *P, const double *Q, const int32_t *kinds, const double *dts, \
+                                   int64_t T, double *z, const double *R, int64_t n, int norm_quats,               \
+                                   uint8_t *flags, double *trace_x, double *trace_P, const double *ea,             \
+                                   const int32_t *augment, void *stream);
+
 /* Per-filter timelines, THE LATE OBSERVATION ON THE DEVICE: the rewind of every filter batch_timeline_plan found late, each in its own ring
  * (EKF_sym.rewind and the too-old test in front of it, the reference's ekf_sym.py:418-438, 464-471), and the gather of the
  * overtaken entries, one replay position of all rewound filters at a time, into the buffers batch_predict_update_kinds and

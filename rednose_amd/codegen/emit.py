@@ -52,12 +52,15 @@ SMALL_MAX_E = 7    # lane-per-filter register budget: x, P and the update's temp
 #                      library without it ({name}_has_batch_run_pf_r() == 0, batch_run_pf_r returns ERR_UNSUPPORTED); k_run_pf and everything else stay
 #   no_run_pf_rd       the same run with a DIAGONAL noise per entry (k_run_dpf / k_run_dpf_tr) touches scratch memory or spills -> library without it
 #                      ({name}_has_batch_run_pf_rd() == 0, batch_run_pf_rd returns ERR_UNSUPPORTED); k_run_pf, k_run_rpf and everything else stay
+#   no_run_pf_ea       the fused run with a schedule per filter of an MSCKF model (k_run_epf: extra arguments per entry, a window shift per filter) touches
+#                      scratch memory or spills -> library without it ({name}_has_batch_run_pf_ea() == 0, batch_run_pf_ea returns ERR_UNSUPPORTED;
+#                      BatchedEKF.run_logs walks such logs step by step)
 #   no_rts4_pf         k_rts4_pf (emit_rts4.kernel(pf=True), two wavefronts per SIMD) spilled, or one of its DPP reads follows the write of its source
 #                      too closely -> rn::k_rts_group<RtsModel, true> serves batch_rts_pf, as rn::k_rts_group serves batch_rts behind no_rts4
 #   no_rts_pf          the smoother with a schedule per filter (the PF = true instantiation of rn::k_rts / rn::k_rts_group) touches scratch memory or
 #                      spills -> library without it ({name}_has_batch_rts_pf() == 0, batch_rts_pf returns ERR_UNSUPPORTED); batch_rts and everything else stay
 FALLBACKS = ("force_wide", "no_model_defaults", "no_rts4", "rts_one_wave", "no_rts", "no_run2", "no_run", "no_run_blk", "no_tri", "no_kinds") + tuple(
-  m.fallback for m in NOISE_MODES) + ("no_rts4_pf", "no_rts_pf")
+  m.fallback for m in NOISE_MODES) + ("no_rts4_pf", "no_rts_pf", "no_run_pf_ea")
 KINDS_MAX = 16      # kinds of a model with a mixed-kind step: the Z table rn::k_timeline_push takes by value
 _active = frozenset()      # fallbacks of the emit() call in progress
 
@@ -90,6 +93,16 @@ def has_run_pf(spec, noise, fallbacks=None):
   if noise.fallback in fb or "no_run_pf" in fb or "no_run" in fb or spec.N > 0 or spec.dim_err > 64:
     return False
   return all(k.ea_sym is None and k.He_sym is None and k.kind > 0 for k in spec.kinds)
+
+
+def has_run_pf_ea(spec, fallbacks=None):
+  """Does this library get the fused run with a schedule per filter of MSCKF models (emit_wide3.run_epf_kernel: k_run_epf, with extra arguments
+  per entry, the predicated null-space projection and a window shift per filter)?  MSCKF models with a fused run; every other model is served by
+  has_run_pf()'s kernels (a model outside the MSCKF family that has a kind with extra arguments takes BatchedEKF.run_logs' step walk)."""
+  fb = _active if fallbacks is None else fallbacks
+  if "no_run_pf_ea" in fb or "no_run" in fb or spec.N <= 0 or spec.dim_err > 64 or family(spec, fb) != "wide":
+    return False
+  return all(k.kind > 0 for k in spec.kinds)
 
 
 def run_pf(spec, fallbacks=None):
@@ -205,15 +218,17 @@ RUN_PARAMS = ("double *x, double *P, const double *Q, const int32_t *kinds, cons
               "uint8_t *flags, double *trace_x, double *trace_P, const double *ea, const int32_t *augment, void *stream")
 RUN_PF_PARAMS = ("double *x, double *P, const double *Q, const int32_t *kinds, const double *dts, int64_t T, double *z, const double *R, int64_t n, int norm_quats, "
                  "uint8_t *flags, double *trace_x, double *trace_P, void *stream")
+RUN_PF_EA_PARAMS = RUN_PF_PARAMS.replace("void *stream", "const double *ea, const int32_t *augment, void *stream")
 RTS_PF_PARAMS = ("const double *xf, const double *Pf, const double *dts, const uint8_t *act, int64_t T, const double *Q, int64_t n, int norm_quats, double *xs, "
                  "double *Ps, const double *x_last, const double *P_last, void *stream")
 RTS_PARAMS = ("const double *xf, const double *Pf, const double *ts, int64_t T, const double *Q, int64_t n, int norm_quats, double *xs, double *Ps, "
               "const double *x_last, const double *P_last, void *stream")
 
 
-def _run_body(launch, hip_check=True, r_per_entry=False):
-  """r_per_entry: R is (T, n, zmax^2) (batch_run_pf_r) or (T, n, zmax) (batch_run_pf_rd), read by the lanes and 16-byte aligned like x, P and z."""
-  return _batched("n >= 0 && T >= 0 && x && P && Q && kinds && dts && z && R", ["x", "P", "z", "trace_x", "trace_P"] + (["R per entry"] if r_per_entry else []),
+def _run_body(launch, hip_check=True, r_per_entry=False, ea=False):
+  """r_per_entry: R is (T, n, zmax^2) (batch_run_pf_r) or (T, n, zmax) (batch_run_pf_rd), read by the lanes and 16-byte aligned like x, P and z.
+  ea: the extra arguments are required (batch_run_pf_ea)."""
+  return _batched("n >= 0 && T >= 0 && x && P && Q && kinds && dts && z && R" + (" && ea" if ea else ""), ["x", "P", "z", "trace_x", "trace_P"] + (["R per entry"] if r_per_entry else []),
                   launch, empty="n == 0 || T == 0", hip_check=hip_check)
 
 
@@ -332,6 +347,27 @@ __global__ __launch_bounds__(64) void k_augment(double* __restrict__ gx, double*
   __shared__ double s_x[{D}];
   const int lane = threadIdx.x;
   for (int64_t f = blockIdx.x; f < n; f += gridDim.x) {{
+    for (int i = lane; i < {D}; i += 64) s_x[i] = gx[f * {D} + i];
+    for (int i = lane; i < {EE}; i += 64) s_P[i] = gP[f * {EE} + i];
+    rn::wave_lds_sync();
+    for (int i = lane; i < {D}; i += 64) {{
+      const int src = i < {d1} ? i : (i < {D - d3} ? i + {d3} : i - {D - d3});
+      gx[f * {D} + i] = s_x[src];
+    }}
+    for (int i = lane; i < {EE}; i += 64) {{
+      const int r = i / {E}, c = i % {E};
+      gP[f * {EE} + i] = s_P[aug_src_err(r) * {E} + aug_src_err(c)];
+    }}
+    rn::wave_lds_sync();
+  }}
+}}
+// ---- the same shift for the filters with active[f] != 0 (active == nullptr: every filter); the others are neither read nor written ----
+__global__ __launch_bounds__(64) void k_augment_m(double* __restrict__ gx, double* __restrict__ gP, const uint8_t* __restrict__ active, const int64_t n) {{
+  __shared__ double s_P[{EE}];
+  __shared__ double s_x[{D}];
+  const int lane = threadIdx.x;
+  for (int64_t f = blockIdx.x; f < n; f += gridDim.x) {{
+    if (active != nullptr && active[f] == 0) continue;      // (uniform over the workgroup)
     for (int i = lane; i < {D}; i += 64) s_x[i] = gx[f * {D} + i];
     for (int i = lane; i < {EE}; i += 64) s_P[i] = gP[f * {EE} + i];
     rn::wave_lds_sync();
@@ -516,6 +552,8 @@ def _abi_batched(spec, s):
   if spec.N > 0:
     a.fn("int", "batch_augment", "double *x, double *P, int64_t n, void *stream",
          _batched("n >= 0 && x && P", [], "  hipLaunchKernelGGL(k_augment, dim3(rn::grid_for_tiles(n)), dim3(64), 0, (hipStream_t)stream, x, P, n);"))
+    a.fn("int", "batch_augment_masked", "double *x, double *P, const uint8_t *active, int64_t n, void *stream",
+         _batched("n >= 0 && x && P", [], "  hipLaunchKernelGGL(k_augment_m, dim3(rn::grid_for_tiles(n)), dim3(64), 0, (hipStream_t)stream, x, P, active, n);"))
   a.fn("void", "msckf_dims", "int *dims",
        f"dims[0] = {spec.dim_main}; dims[1] = {spec.dim_main_err}; dims[2] = {spec.dim_augment}; dims[3] = {spec.dim_augment_err}; dims[4] = {spec.N};")
   a.fn("int", "kind_eadim", "int kind", _switch(spec, ea_len))
@@ -546,6 +584,12 @@ def _abi_batched(spec, s):
     launch = (emit_small if s.fam == "small" else emit_wide3).launch_run_pf(noise)
     a.fn("int", sym, RUN_PF_PARAMS, _run_body(launch, r_per_entry=noise.per_entry) if has else _unsupported(
       f"{sym}: not generated for this model (MSCKF model, a kind with extra arguments, no fused run, or the kernel did not fit the register file)"))
+  # The same run for MSCKF models (k_run_epf): batch_run_pf with `ea` (T, n, EA), EA the largest kind_eadim, and `augment` (T, n) or NULL -- a
+  # window shift of filter i after its entry t.  The symbols exist in every library; without the kernel batch_run_pf_ea returns ERR_UNSUPPORTED.
+  has = has_run_pf_ea(spec)
+  a.fn("int", "has_batch_run_pf_ea", "void", f"return {int(has)};")
+  a.fn("int", "batch_run_pf_ea", RUN_PF_EA_PARAMS, _run_body(emit_wide3.launch_run_epf(), ea=True) if has else _unsupported(
+    "batch_run_pf_ea: not generated for this model (not an MSCKF model, no fused run, or the kernel did not fit the register file)"))
   return a
 
 

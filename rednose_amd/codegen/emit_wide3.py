@@ -105,7 +105,7 @@ class RunLayout(SlotLayout):
     return self.feature_tail(self.OFF_FL + 1)
 
 
-def predict_fn(spec, qdiag=False, pf=False):
+def predict_fn(spec, qdiag=False, pf=False, sfx="_pf"):
   """Matrix part of predict on register rows; F's non-trivial entries are broadcast reads of the filter's slot.
 
   P' = F P F^T + dt Q with ONE transposition through LDS: rows of A = P F^T are row-local; under P = P^T the columns of A are the
@@ -169,7 +169,7 @@ def predict_fn(spec, qdiag=False, pf=False):
   b += _tl(9)
   rows = ", ".join(f"double (&row{s})[{E}]" for s in range(R))
   idx = ", ".join(f"const int rr{s}, const int rc{s}, const bool ok{s}" for s in range(R))
-  sfx, pda = ("_pf", ", const bool pd") if pf else ("", "")
+  sfx, pda = (sfx, ", const bool pd") if pf else ("", "")      # (sfx="_epf": the same text under the names k_run_epf calls)
   if qdiag:
     qarg = ", ".join(f"const double qd{s}" for s in range(R))
     head = (f"__device__ __forceinline__ void predict_rows_qd{sfx}({rows}, double* sP, {qarg}, const double* sl, {idx}{pda}{_tl_arg()}) {{")
@@ -178,7 +178,7 @@ def predict_fn(spec, qdiag=False, pf=False):
   return "\n".join([head] + ind(b) + ["}"])
 
 
-def update_fn(spec, k, pf=False, noise=TABLE):
+def update_fn(spec, k, pf=False, noise=TABLE, sfx=None):
   """Matrix part of the update of kind k on register rows.  y, the non-trivial entries of He = H H_mod and, for feature-track
   kinds, the Householder reflectors and the projected noise are read from the filter's slot (phase 1 put them there); dx and
   the gate / rank flags go back to it.
@@ -188,6 +188,10 @@ def update_fn(spec, k, pf=False, noise=TABLE):
   takes zero coefficients into both rank-Z passes (row -+= 0 * 0: the rows come out unchanged, whatever stale numbers its slot holds), and
   writes nothing into its slot.
 
+  A feature-track kind with pf=True (k_run_epf, MSCKF models; sfx="_epf" names the function `update_{kind}_rows_epf`): `mine` goes through the null-space
+  projection.  The projected noise, rank_deficient and the reflectors of the slot mean something only where `mine`; any other group's slot is stale (NaN at
+  first), and it takes R = I, rank_deficient = 0 and HPH = 0 by select -- S = I --, beside the zeroed coefficients and the guarded slot writes above.
+
   noise=ENTRY (with pf) emits `update_{kind}_rows_rpf` for k_run_rpf, whose R is per entry: the same statements, except that `gR` is the group's OWN
   row and its Z * Z doubles are taken only where `mine` -- the row of a group that is idle, flagged 8 or of another kind may hold anything, NaN
   included, and such a group factors the identity instead (its coefficients are zeroed either way, but 0 * NaN is NaN).
@@ -195,7 +199,7 @@ def update_fn(spec, k, pf=False, noise=TABLE):
   noise=DIAG (with pf) emits `update_{kind}_rows_dpf` for k_run_dpf, whose R is the group's own row of Z variances, taken only where `mine` (ones
   otherwise: the identity as above).  The noise stays a vector through the update -- S = HPH with S[i][i] += r[i], the gate's 1e16 on the Z
   variances, the Joseph term K R as kk[zi] * r[zi] -- so Z doubles live where the other flavours hold Z * Z."""
-  assert not (pf and k.He_sym is not None) and (pf or noise is TABLE)
+  assert (pf or noise is TABLE) and not (k.He_sym is not None and noise is not TABLE)
   E, Zf = spec.dim_err, k.zdim
   _, R, _ = layout(spec)
   lay, _, Hss, _ = w2.slot_tables(spec, RunLayout)
@@ -211,6 +215,9 @@ def update_fn(spec, k, pf=False, noise=TABLE):
   b = ["(void)sP;"] + ([] if lean else [f"double R[{Z if noise.diag else Z * Z}];"])
   if lean:
     b += ["int rz = 0;", 'asm volatile("" : "+v"(rz));', "const double* gRv = gR + rz;      // a vector address: R stays out of the scalar registers"]
+  elif feat and pf:      # the slot of a group that is not `mine` is stale (NaN at first): the identity and 0 by select, never by product
+    b += ["#pragma unroll", f"for (int i = 0; i < {Z * Z}; i++) R[i] = mine ? sl[{lay.OFF_RP} + i] : ((i % {Z + 1} == 0) ? 1.0 : 0.0);      // A^T R A (phase 1)",
+          "(void)gR;", f"const double rank_deficient = mine ? sl[{lay.OFF_FL}] : 0.0;      // 4.0 when phase 1 found Hea rank deficient"]
   elif feat:
     b += ["#pragma unroll", f"for (int i = 0; i < {Z * Z}; i++) R[i] = sl[{lay.OFF_RP} + i];      // A^T R A (phase 1)", "(void)gR;",
           f"const double rank_deficient = sl[{lay.OFF_FL}];      // 4.0 when phase 1 found Hea rank deficient"]
@@ -245,7 +252,8 @@ def update_fn(spec, k, pf=False, noise=TABLE):
       b.append("{")
       b.append(f"  double m[{Zf}] = {{" + ", ".join(sum_terms(term(cf, f'sG[{zi} * {E} + {j}]') for j, cf in Hs.row_nz(w)) for w in range(Zf)) + "};")
       b.append(f"  rn::apply_reflectors<{Zf}, {EADIM}>(sl + {RF}, sl + {RB}, m);")
-      b += ["#pragma unroll", f"  for (int w = 0; w < {Z}; w++) HPH[{zi * Z} + w] = m[{EADIM} + w];", "}"]
+      # (pf: a group that is not `mine` put zeros where G goes, but its reflectors are stale: S = R = I for it, by select)
+      b += ["#pragma unroll", f"  for (int w = 0; w < {Z}; w++) HPH[{zi * Z} + w] = {'mine ? ' if pf else ''}m[{EADIM} + w]{' : 0.0' if pf else ''};", "}"]
   else:
     for zi in range(Z):
       for w in range(Z):
@@ -295,7 +303,7 @@ def update_fn(spec, k, pf=False, noise=TABLE):
   b.append("rn::wave_lds_sync();      // the broadcast buffer is free again")
   rows = ", ".join(f"double (&row{s})[{E}]" for s in range(R))
   idx = ", ".join(f"const int rr{s}, const int rc{s}, const bool ok{s}" for s in range(R))
-  head = (f"__device__ __forceinline__ void update_{k.kind}_rows{noise.update if pf else ''}({rows}, const double* __restrict__ gR, double* sP, "
+  head = (f"__device__ __forceinline__ void update_{k.kind}_rows{(sfx or noise.update) if pf else ''}({rows}, const double* __restrict__ gR, double* sP, "
           f"double* sG, const double* sl, double* sw, {idx}{', const bool mine' if pf else ''}{_tl_arg()}) {{")
   return "\n".join([head] + ind(b) + ["}"])
 
@@ -316,6 +324,10 @@ def kernels(spec, with_run=True):
   for noise in NOISE_MODES:
     if emit.has_run_pf(spec, noise):
       pf += [update_fn(spec, k, pf=True, noise=noise) for k in spec.kinds] + [run_pf_kernel(spec, noise)]
+  # MSCKF models: the same run with extra arguments per entry, the predicated null-space projection and a window shift per group (k_run_epf)
+  if emit.has_run_pf_ea(spec):
+    pf += ([predict_fn(spec, pf=True, sfx="_epf"), predict_fn(spec, qdiag=True, pf=True, sfx="_epf")] +
+           [update_fn(spec, k, pf=True, sfx="_epf") for k in spec.kinds] + [run_epf_kernel(spec)])
   if not with_run:
     # the model's batch_run is emit_run2's k_run2; the fused run with a schedule per filter is this module's single-wavefront structure:
     # the scalar phases against RunLayout, the predicated matrix phases and k_run_pf follow the constants
@@ -359,9 +371,9 @@ def _row_args(R):
   return ", ".join(f"row{s}" for s in range(R)), ", ".join(f"rr{s}, rc{s}, ok{s}" for s in range(R))
 
 
-def _img(E, R, cond=""):
+def _img(E, R, cond="", pad=""):
   """rows -> LDS image (only where something reads the image: trace, window shift, the final store)"""
-  return "\n".join(f"        if (ok{s}{cond}) {{\n#pragma unroll\n          for (int j = 0; j < {E}; j++) sP[rr{s} * {E} + j] = row{s}[j];\n        }}" for s in range(R))
+  return "\n".join(f"{pad}        if (ok{s}{cond}) {{\n#pragma unroll\n{pad}          for (int j = 0; j < {E}; j++) sP[rr{s} * {E} + j] = row{s}[j];\n{pad}        }}" for s in range(R))
 
 
 def _stamp(ph):
@@ -372,7 +384,7 @@ def _stamp(ph):
           "g_tl[(blockIdx.x * 64 + ti_) * 2] = __builtin_readcyclecounter(); g_tl[(blockIdx.x * 64 + ti_) * 2 + 1] = wall_clock64(); }")
 
 
-def _fused_run(spec, pf, *, title, sched, update, flags_rule, args="", unused="", pre_loop="", after_step="", kname=None):
+def _fused_run(spec, pf, *, title, sched, update, flags_rule, args="", unused="", pre_loop="", after_step="", kname=None, fsfx="_pf"):
   """The text of a single-wavefront fused run, once: kernel head, LDS, the tile prologue (images, slots, observations, rows into registers), the
   step loop (predict, update, inject, y and the trace out, the next observation in) and the write-back.  `pf`: a schedule per filter (k_run_pf)
   instead of a shared one (k_run) -- the predicates of the predict phase, the predicated matrix functions, the write-back into the image
@@ -402,7 +414,7 @@ def _fused_run(spec, pf, *, title, sched, update, flags_rule, args="", unused=""
   def note(text):      # k_run's remarks; k_run_pf refers to k_run
     return "" if pf else text
   stamp = (lambda ph: "") if pf else _stamp
-  step, pd, any_pd, fsfx, pda = ("step", "pd", "__any(pd)", "_pf", ", pd") if pf else ("live", "do_pred", "do_pred", "", "")
+  step, pd, any_pd, fsfx, pda = ("step", "pd", "__any(pd)", fsfx, ", pd") if pf else ("live", "do_pred", "do_pred", "", "")
   le_decl = f"""    int le = lane;
     asm volatile("" : "+v"(le));{note("         // (same: nothing of the first copy's index arithmetic is kept alive across the step loop)")}
 """
@@ -532,12 +544,8 @@ def run_kernel(spec):
     mat_cases.append(f"        case {k.kind}: update_{k.kind}_rows({rows}, gR + t * {zmax * zmax}, sP, s_G + gg * {zmax * E}, sl, sl, {idx}{_tl_arg(True)}); break;")
   aug = ""
   if spec.N > 0:
-    d1, d2, d3, d4 = spec.dim_main, spec.dim_main_err, spec.dim_augment, spec.dim_augment_err
-    src_x = [i if i < d1 else (i + d3 if i < D - d3 else i - (D - d3)) for i in range(D)]
-
-    def se(i):
-      r = i if i < E - d4 else i - (E - d4)
-      return r if r < d2 else r + d4
+    d2, d4 = spec.dim_main_err, spec.dim_augment_err
+    src_x, se = _shift_maps(spec)
     shift = []
     for s in range(R):
       shift.append(f"        {{ const int sr = (rc{s} < {E - d4} ? rc{s} : rc{s} - {E - d4}); const int srow = sr < {d2} ? sr : sr + {d4};")
@@ -668,6 +676,123 @@ def run_pf_kernel(spec, noise=TABLE):
 {mat}{r_next}""",
     flags_rule=f"""        int fl = kind <= 0 ? 16 : 8;          // idle entry; a kind the model does not have: untouched either way
         if (step) fl = scal_inject_r(sl, sl + {lay.OFF_X}, norm_quats) | (int)sl[{lay.OFF_FL}];""")
+
+
+def _shift_maps(spec):
+  """The MSCKF window shift (EKF_sym.augment, ekf_sym.py:365-391) as fixed permutations -> (src_x, se): new state entry i is old entry
+  src_x[i], new row / column i of P is old row / column se(i)."""
+  D, E = spec.dim_x, spec.dim_err
+  d1, d2, d3, d4 = spec.dim_main, spec.dim_main_err, spec.dim_augment, spec.dim_augment_err
+  src_x = [i if i < d1 else (i + d3 if i < D - d3 else i - (D - d3)) for i in range(D)]
+
+  def se(i):
+    r = i if i < E - d4 else i - (E - d4)
+    return r if r < d2 else r + d4
+  return src_x, se
+
+
+def run_epf_kernel(spec):
+  """k_run_epf, MSCKF models: k_run_pf (one R per kind) with what k_run alone carried so far, per filter.
+    * EXTRA ARGUMENTS PER ENTRY: gea is (T, n, EA), EA the largest kind_eadim.  Lane c == 0 of a group that steps a kind with extra arguments
+      reads its own row (t n + base + g) EA inside that kind's scalar phase; no other row is read (idle entries, entries of an unknown kind
+      and of kinds without extra arguments may hold NaN there).
+    * FEATURE-TRACK KINDS: `update_{kind}_rows_epf` (update_fn(pf=True)) carries `mine` through the null-space-projected update.  The projected
+      noise, rank_deficient and the reflectors of the slot mean something only where `mine`; any other group takes the identity, 0 and zero
+      coefficients by SELECT (its slot is stale, NaN at first, and 0 * NaN is NaN) and writes nothing into its slot.
+    * A WINDOW SHIFT PER FILTER: augs is (T, n) or NULL, fetched a step ahead with kind and dt.  After step t the groups with step && aug != 0
+      shift, with the arithmetic of k_run's block: the image is written from the rows, lane 0 permutes x, the rows are re-read through the
+      fixed permutation -- every lane meets both fences, only the shifting groups take the new rows and write x (the others masked off).
+      The block is skipped when no group of the wavefront shifts.  An entry that did not step its filter (idle, unknown kind) does not shift
+      it; one whose projection was rank deficient (flag 4) does, as in k_run.  The trace row is the estimate BEFORE the shift.
+  (_fused_run holds the kernel's text.)"""
+  D, E = spec.dim_x, spec.dim_err
+  _, R, _ = layout(spec)
+  lay = w2.slot_tables(spec, RunLayout)[0]
+  zmax = max(k.zdim for k in spec.kinds)
+  ZZ, EAM = zmax * zmax, ea_max(spec)
+  rows, idx = _row_args(R)
+  nlc = chr(10)
+  known = " ".join(f"case {k.kind}:" for k in spec.kinds)
+  scal_cases, mat = [], []
+  for i, k in enumerate(spec.kinds):
+    feat = k.He_sym is not None
+    args = f"sl, sl + {lay.OFF_Y}"
+    if ea_count(k):
+      args += f", gea + ((int64_t)t * n + base + g) * {EAM}"
+    if feat:
+      args += f", gR + {i * ZZ}"
+    scal_cases.append(f"          case {k.kind}: scal_obs_{k.kind}_r{'<true>' if feat else ''}({args}); break;")
+    mat.append(f"""      {{
+        const bool mine = step && kind == {k.kind};
+        if (__any(mine)) update_{k.kind}_rows_epf({rows}, gR + {i * ZZ}, sP, s_G + gg * {zmax * E}, sl, sl, {idx}, mine{_tl_arg(True)});
+      }}""")
+  src_x, se = _shift_maps(spec)
+  d2, d4 = spec.dim_main_err, spec.dim_augment_err
+  shift = []
+  for s in range(R):
+    # (a branch on the group's predicate, not a select per entry: with `row = sh ? image : row` hipcc kept the row arrays in scratch memory,
+    # 256 bytes per lane on the 15-state model; the lanes of the other groups are masked off through the same statements)
+    shift.append(f"          if (sh) {{ const int sr = (rc{s} < {E - d4} ? rc{s} : rc{s} - {E - d4}); const int srow = sr < {d2} ? sr : sr + {d4};")
+    shift += [f"            row{s}[{j}] = sP[srow * {E} + {se(j)}];" for j in range(E)]
+    shift.append("          }")
+  aug = f"""
+      // MSCKF window shift after this step, per group (k_run's block under the group's own predicate; the trace above holds the estimate
+      // BEFORE the shift): every lane meets the fences, only the shifting groups take the new rows and write x
+      {{
+        const bool sh = step && aug != 0;
+        if (__any(sh)) {{
+{_img(E, R, pad="  ")}
+          rn::wave_lds_sync();
+          if (c == 0 && sh) {{
+            double xo[{D}];
+#pragma unroll
+            for (int i = 0; i < {D}; i++) xo[i] = sl[{lay.OFF_X} + i];
+{nlc.join(f"            sl[{lay.OFF_X + i}] = xo[{src_x[i]}];" for i in range(D) if src_x[i] != i)}
+          }}
+{nlc.join(shift)}
+          rn::wave_lds_sync();
+        }}
+      }}"""
+  id0_guard = "true" if not spec.identity_at_dt0() else "dt != 0.0"
+  return _fused_run(
+    spec, True, kname="k_run_epf",
+    title=(f"// ---- fused multi-step run, a schedule per filter, MSCKF models: k_run_pf (gR one row per kind) with gea (T, n, {EAM}) extra arguments per entry "
+           "and augs (T, n) or NULL, a window shift after the entry, per group (see emit_wide3.run_epf_kernel) -----------"),
+    args=", const double* __restrict__ gea, const int32_t* __restrict__ augs",
+    pre_loop="""    bool stepped = false;
+    // the group's own schedule entry, a step ahead (every lane of a group reads its filter's: one address per group)
+    int kind_n = kinds[base + gg];
+    double dt_n = dts[base + gg];
+    int aug_n = augs != nullptr ? augs[base + gg] : 0;
+""",
+    sched=f"""      const int kind = live ? kind_n : 0;
+      const double dt = dt_n;
+      const int aug = aug_n;
+      {{
+        const int64_t tn = t + 1 < T ? t + 1 : t;
+        kind_n = kinds[tn * n + base + gg];
+        dt_n = dts[tn * n + base + gg];
+        if (augs != nullptr) aug_n = augs[tn * n + base + gg];
+      }}
+      bool step = false;
+      switch (kind) {{ {known} step = true; break; default: break; }}
+      const bool pd = step && ({id0_guard});
+      stepped = stepped || step;""",
+    update=f"""      if (c == 0 && step) {{
+        switch (kind) {{
+{nlc.join(scal_cases)}
+          default: break;
+        }}
+      }}
+      rn::wave_lds_sync();
+{nlc.join(mat)}""",
+    flags_rule=f"""        int fl = kind <= 0 ? 16 : 8;          // idle entry; a kind the model does not have: untouched either way
+        if (step) fl = scal_inject_r(sl, sl + {lay.OFF_X}, norm_quats) | (int)sl[{lay.OFF_FL}];""",
+    after_step=aug, fsfx="_epf").strip("\n")      # (one title line, no blank line around: tools/emit_digest.py --without k_run_epf takes exactly this text out)
+
+
+def launch_run_epf():
+  return _launch("k_run_epf", ", ea, augment")
 
 
 def _launch(kname, more=""):

@@ -81,6 +81,10 @@ def gen_code(folder, name, f_sym, dt_sym, x_sym, obs_eqs, dim_x, dim_err, eskf_p
                                          "without it") if pf_bad else (usage, bad)
       for noise in reversed(NOISE_MODES):
         usage, bad = drop(noise)
+      if "k_run_epf" in bad:
+        # an MSCKF model's fused run with a schedule per filter: this kernel alone is dropped ({name}_has_batch_run_pf_ea() == 0), batch_run stays
+        usage, bad = fall_back("no_run_pf_ea", "the fused run with a schedule per filter, extra arguments and window shifts per entry does not fit the register "
+                                               "file: library without it")
       if "k_rts4_pf" in bad:
         # like no_rts4 for batch_rts: the lane-group smoother's per-filter instantiation serves batch_rts_pf instead
         usage, bad = fall_back("no_rts4_pf", "the register-broadcast smoother with a schedule per filter spills under its two-wavefronts-per-SIMD budget (or a DPP "
@@ -483,6 +487,7 @@ class BatchedEKF:
     self.N = N
     self.dim_main, self.dim_augment, self.dim_augment_err = dim_main, dim_augment, dim_augment_err
     self.augment_times = [0] * N
+    self._augment_times_pf = None      # (N, n_window) per-filter shift times of run_logs (filter_augment_times())
 
     # always the ctypes binding: every argument below is a ctypes value (device pointers, stream handles, None), which a
     # cffi-dlopen'ed library would reject; EKF_sym keeps the reference's cffi-first loader for its host-pointer calls
@@ -1698,7 +1703,17 @@ class BatchedEKF:
   def _has_batch_run_pf_rd(self):
     return self._has_sym("batch_run_pf_rd")
 
-  def run_logs(self, ts, kinds, zs, Rs, trace=False, flags=False, out=None, exact=False):
+  def _has_batch_run_pf_ea(self):
+    return self._has_sym("batch_run_pf_ea")
+
+  def filter_augment_times(self):
+    """(N, n_window) array: every filter's own last n_window window-shift times, as run_logs(augment=...) recorded them (the per-filter
+    counterpart of get_augment_times(), which keeps the shifts of shared timelines); zeros until a filter has shifted, as the constructor's."""
+    if self._augment_times_pf is None:
+      self._augment_times_pf = np.zeros((self.batch, self.N))
+    return self._augment_times_pf.copy()
+
+  def run_logs(self, ts, kinds, zs, Rs, trace=False, flags=False, out=None, exact=False, extra_args=None, augment=None):
     """Replay N recorded logs, one per filter, in ONE launch ({name}_batch_run_pf: the fused run with a schedule per filter; objects built
     with per_filter=True).  ts (T, N): the time of entry t of filter i's log, NaN where the filter has none; kinds (T, N) ints, <= 0 = no
     entry (idle); zs (T, N, zmax): the first Z of a row are the observation, consumed -- overwritten by the residual, the rest of the row and
@@ -1730,7 +1745,16 @@ class BatchedEKF:
     The covariance is read as (P + P^T) / 2, the fused runs' contract.  exact=True, or a library without the kernel
     ({name}_has_batch_run_pf() == 0: MSCKF models, kinds with extra arguments, models without a fused run), walks the same schedule with the step-granular entry points, one
     batch_predict_update_kinds launch per step where the library has it, else one `_masked` launch per kind present in the step; exact=True
-    leaves an asymmetric P as it is, like run(exact=True).  Kinds that take extra arguments are not served."""
+    leaves an asymmetric P as it is, like run(exact=True).
+
+    extra_args (T, N, EA), EA the largest {name}_kind_eadim: row (t, i) starts with the extra arguments of filter i's entry t (a feature track's
+    landmark); rows of idle entries and of kinds without extra arguments are never read and may hold anything.  A log with a kind that takes
+    extra arguments and no extra_args raises KalmanError.  augment (T, N) bool / int, MSCKF models only (KalmanError otherwise): the window of
+    filter i shifts after its entry t (EKF_sym.augment); set where kinds <= 0 it is ignored.  The trace row of such an entry is the estimate
+    BEFORE the shift, as in run(); filter_augment_times() keeps every filter's own shift times.  An MSCKF model's logs with shared (Z, Z) noise
+    are ONE launch of {name}_batch_run_pf_ea where the library has it ({name}_has_batch_run_pf_ea()); with exact=True, without the kernel or
+    with a noise per entry the step walk passes each kind's extra arguments to its `_masked` launch and follows a step in which any filter
+    shifts with one {name}_batch_augment_masked."""
     torch = self._torch
     if not self.per_filter:
       raise KalmanError("run_logs replays per-filter timelines: construct the orchestrator with per_filter=True")
@@ -1754,8 +1778,23 @@ class BatchedEKF:
     for k in present:
       if k not in self.zdims or (isinstance(Rs, dict) and k not in Rs):
         raise KeyError(k)
-      if self.eadims.get(k, 0):
-        raise KalmanError(f"run_logs: kind {k} takes extra arguments, which a per-filter schedule does not carry")
+      if self.eadims.get(k, 0) and extra_args is None:
+        raise KalmanError(f"run_logs: kind {k} takes extra arguments: pass extra_args (T, N, {max(self.eadims.values())})")
+    EA = max(list(self.eadims.values()) + [0])
+    ea = None
+    if extra_args is not None and EA > 0:
+      shape = tuple(extra_args.shape) if hasattr(extra_args, "shape") else np.shape(extra_args)
+      if shape != (T, N, EA):
+        raise KalmanError(f"run_logs: extra_args must be (T, N, EA) = ({T}, {N}, {EA}), got {shape}")
+      ea = self._dev(extra_args)
+    ag = None
+    if augment is not None:
+      if not self.msckf:
+        raise KalmanError("run_logs: augment shifts the window of an MSCKF model; this model has none")
+      ag = augment if isinstance(augment, torch.Tensor) else torch.as_tensor(np.asarray(augment))
+      if tuple(ag.shape) != (T, N):
+        raise KalmanError(f"run_logs: augment must be (T, N) = ({T}, {N}), got {tuple(ag.shape)}")
+      ag = ((ag.to(self.device) != 0) & (kd > 0)).to(torch.int32).contiguous()      # (ignored at idle entries)
     Rd, noise = self._run_logs_noise(Rs, kd, T, diag_ok=self._has_batch_run_pf_rd() and not exact)
     ft0 = self.filter_times()
     dts, last = self._log_dts(tt, kd, ft0, "run_logs")
@@ -1771,11 +1810,24 @@ class BatchedEKF:
     fl = torch.zeros((T, N), dtype=torch.uint8, device=self.device) if flags else None
     # (DIAG comes only with its kernel and exact false: _run_logs_noise expands the variances otherwise)
     has = {TABLE: self._has_batch_run_pf, ENTRY: self._has_batch_run_pf_r, DIAG: self._has_batch_run_pf_rd}[noise]
-    if has() and not exact:
+    if self.msckf and noise is TABLE and not exact and self._has_batch_run_pf_ea():
+      ea_k = ea if ea is not None else torch.zeros(2, dtype=torch.float64, device=self.device)      # (no kind of the log reads it)
+      self._call("batch_run_pf_ea", self._p(self.x), self._p(self.P), self._p(self.Q), self._p(kd), self._p(dts), T, self._p(zs), self._p(Rd), N,
+                 self.norm_quats, self._p(fl), self._p(tx), self._p(tP), self._p(ea_k), self._p(ag), self._stream())
+      self._keepalive_ea = (ea_k, ag)
+    elif self.msckf or ea is not None:      # no kernel of batch_run_pf's family carries extra arguments or window shifts
+      self._run_logs_stepwise(kd, dts, zs, Rd, fl, tx, tP, symmetrise=not exact, per_entry=noise.per_entry, ea=ea, ag=ag)
+    elif has() and not exact:
       self._call(f"batch_run_pf{noise.sfx}", self._p(self.x), self._p(self.P), self._p(self.Q), self._p(kd), self._p(dts), T, self._p(zs), self._p(Rd), N,
                  self.norm_quats, self._p(fl), self._p(tx), self._p(tP), self._stream())
     else:
       self._run_logs_stepwise(kd, dts, zs, Rd, fl, tx, tP, symmetrise=not exact, per_entry=noise.per_entry)
+    if ag is not None:      # every filter's own shift times, in the order of its log
+      at, agh, th = self.filter_augment_times(), ag.cpu().numpy() != 0, tt.cpu().numpy()
+      for t in np.nonzero(agh.any(axis=1))[0]:
+        m = agh[t]
+        at[m] = np.concatenate([at[m, 1:], th[t, m, None]], axis=1)
+      self._augment_times_pf = at
     self.filter_time = ft_new
     self._ft_dev = None
     if self.rewind_to_keep > 0:
@@ -1870,12 +1922,15 @@ class BatchedEKF:
                   embed(self._dev(var[k]), self.zdims[k]) if k in var else
                   self._dev(shared[k]).expand(T, N, self.zdims[k] ** 2) if k in shared else None), ENTRY
 
-  def _run_logs_stepwise(self, kd, dts, zs, Rd, fl, tx, tP, symmetrise=True, per_entry=False):
+  def _run_logs_stepwise(self, kd, dts, zs, Rd, fl, tx, tP, symmetrise=True, per_entry=False, ea=None, ag=None):
     """run_logs() for a library without the fused kernel, and run_logs(exact=True): the same per-filter schedule, step by step.
-    per_entry: Rd is (T, N, zmax^2), and step t takes Rd[t] with r_per_filter = 1 (the `_masked` walk: that kind's rows compacted to (N, Z^2))."""
+    per_entry: Rd is (T, N, zmax^2), and step t takes Rd[t] with r_per_filter = 1 (the `_masked` walk: that kind's rows compacted to (N, Z^2)).
+    ea (T, N, EA): a kind with extra arguments takes ea[t] in its `_masked` launch; ag (T, N) int32: a step in which any filter shifts its
+    window is followed by one batch_augment_masked on those filters (the trace rows are taken before it)."""
     torch = self._torch
     T, N = kd.shape
-    mixed = self._has_step_kinds()
+    mixed = self._has_step_kinds() and ea is None
+    ag_any = None if ag is None else ag.any(dim=1).cpu().numpy()
     if symmetrise:      # the fused kernel's contract: (P + P^T) / 2 for every filter that steps, a filter without an entry leaves as it came
       stepped = (kd > 0).any(dim=0)
       self.P.copy_(torch.where(stepped[:, None, None], 0.5 * (self.P + self.P.transpose(1, 2)), self.P))
@@ -1904,11 +1959,14 @@ class BatchedEKF:
           else:
             Rk = Rd[self.kinds.index(k), :Z * Z].clone()
           fk = torch.zeros(N, dtype=torch.uint8, device=self.device)
+          eak = None
+          if self.eadims.get(k, 0):      # this kind's rows; zeros where a filter brings another kind or none (its row may hold anything)
+            eak = torch.where(m8[:, None] != 0, ea[t, :, :self.eadims[k]], torch.zeros((), dtype=torch.float64, device=self.device)).contiguous()
           self._call(f"batch_predict_update_{k}_masked", self._p(self.x), self._p(self.P), self._p(self.Q), self._p(dt), 0.0, self._p(zk), self._p(Rk),
-                     int(per_entry), None, N, self.norm_quats, self._p(fk), self._p(m8), self._stream())
+                     int(per_entry), self._p(eak), N, self.norm_quats, self._p(fk), self._p(m8), self._stream())
           zt[:, :Z] = torch.where(m8[:, None] != 0, zk, zt[:, :Z])
           flt.copy_(torch.where(m8 != 0, fk, flt))
-          keep = keep[-len(self.kinds):] + [(m8, zk, Rk, fk, dt)]
+          keep = keep[-len(self.kinds):] + [(m8, zk, Rk, fk, dt, eak)]
       zs[t].copy_(zt)
       if fl is not None:
         fl[t].copy_(flt)
@@ -1916,6 +1974,10 @@ class BatchedEKF:
         tx[t].copy_(self.x)
       if tP is not None:
         tP[t].copy_(self.P)
+      if ag_any is not None and ag_any[t]:
+        g8 = (ag[t] != 0).to(torch.uint8)
+        self._call("batch_augment_masked", self._p(self.x), self._p(self.P), self._p(g8), N, self._stream())
+        keep = keep + [(g8,)]
     self._keepalive_step = keep
 
   # -- offline smoothing ----------------------------------------------------------------------------

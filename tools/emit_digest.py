@@ -8,7 +8,8 @@ A change to the emitters that must leave every generated text as it is: run it w
 parent that does not know the knob is checked by comparing that file with the parent's own.  Configurations come and go with the knobs, so two
 digest files are compared by label: every line they share a label for must be the same line (`grep -Fxvf PARENT.txt BRANCH.txt` prints what is not).
 --without takes the named functions of the C ABI ({name}_SUFFIX: prototype and definition) and the named kernels (k_...) out of the texts before
-they are hashed: a change that adds entry points or kernels and must leave everything else as it is gives, with what it adds named, the parent's own lines."""
+they are hashed: a change that adds entry points or kernels and must leave everything else as it is gives, with what it adds named, the parent's own lines.
+A name behind `dev:` is a `__device__` function of the generated text (dev:update_2_rows_epf), taken out the same way."""
 import argparse
 import hashlib
 import os
@@ -25,7 +26,8 @@ FALLBACK_MODELS = {"force_wide": ("kinematic6", "attitude"), "no_run_blk": ("kin
                    "no_run_pf_r": ("kinematic6", "kinematic9", "live"),
                    "no_run_pf_rd": ("kinematic6", "kinematic9", "live", "randz10"),
                    "no_rts4_pf": ("kinematic9", "live"),
-                   "no_rts_pf": ("kinematic6", "kinematic9", "live", "rand24")}      # models on which the fallback changes the text
+                   "no_rts_pf": ("kinematic6", "kinematic9", "live", "rand24"),
+                   "no_run_pf_ea": ("feature", "feature36")}      # models on which the fallback changes the text
 GV_MODELS = ("gv_runtime", "gv_runtime10", "gv_extra")
 LANE_GROUP_KNOBS = {      # of the lane-group family: the branches of its step kernels, the fused runs and the smoother that no default model takes
   "live": ("wide_timeline=1", "wide_lean_q=0", "wide_inline=0", "wide_db=1,wide_ft=16", "wide_lean=0,wide_lb=0,wide_db=-1,wide_ft=0", "run2_prio=3",
@@ -89,8 +91,12 @@ def example_spec(name):
 def without(name, hdr, src, suffixes):
   """(hdr, src) minus the C ABI functions {name}_SUFFIX: their prototypes in the header, their definitions in the source (one-line bodies
   `sig { ... }` and bodies between the braces' own lines, the two forms emit._Abi.fn prints).  A suffix that starts with `k_` names a kernel
-  instead: its `__global__` definition goes, up to the closing brace in the first column, with the `// ----` title line in front of it."""
+  instead: its `__global__` definition goes, up to the closing brace in the first column, with the `// ----` title line in front of it; one
+  that starts with `dev:` a `__device__` function."""
   for sfx in suffixes:
+    if sfx.startswith("dev:"):      # a device function: from its `__device__` line to the closing brace in the first column
+      src = re.sub(r"^__device__[^\n]*\bvoid %s\(.*?^\}\n" % re.escape(sfx[4:]), "", src, flags=re.M | re.S)
+      continue
     if sfx.startswith("k_"):
       src = re.sub(r"(?:^// ----[^\n]*\n\n?)?^__global__[^\n]*\bvoid %s\(.*?^\}\n" % sfx, "", src, flags=re.M | re.S)
       continue
