@@ -522,8 +522,8 @@ __global__ __launch_bounds__(64) void {kname or ("k_run_pf" if pf else "k_run")}
 
 def run_kernel(spec):
   """k_run: the schedule is shared, kinds[t] and dts[t] are wave-uniform, and so is every branch of a step.  Extra arguments, feature-track
-  kinds and the MSCKF window shift exist here only (_fused_run holds the kernel's text)."""
-  D, E = spec.dim_x, spec.dim_err
+  kinds and the MSCKF window shift exist here and, per filter, in k_run_epf (_fused_run holds the kernel's text, _window_shift the shift's)."""
+  E = spec.dim_err
   _, R, _ = layout(spec)
   lay = w2.slot_tables(spec, RunLayout)[0]
   zmax = max(k.zdim for k in spec.kinds)
@@ -542,32 +542,11 @@ def run_kernel(spec):
       args += f", gR + t * {zmax * zmax}"
     scal_cases.append(f"          case {k.kind}: {{ {guard}scal_obs_{k.kind}_r{'<true>' if feat else ''}({args}); break; }}")
     mat_cases.append(f"        case {k.kind}: update_{k.kind}_rows({rows}, gR + t * {zmax * zmax}, sP, s_G + gg * {zmax * E}, sl, sl, {idx}{_tl_arg(True)}); break;")
-  aug = ""
-  if spec.N > 0:
-    d2, d4 = spec.dim_main_err, spec.dim_augment_err
-    src_x, se = _shift_maps(spec)
-    shift = []
-    for s in range(R):
-      shift.append(f"        {{ const int sr = (rc{s} < {E - d4} ? rc{s} : rc{s} - {E - d4}); const int srow = sr < {d2} ? sr : sr + {d4};")
-      shift += [f"          row{s}[{j}] = sP[srow * {E} + {se(j)}];" for j in range(E)]
-      shift.append("        }")
-    nl = chr(10)
-    aug = f"""
+  aug = "" if spec.N <= 0 else f"""
       // MSCKF window shift after this step (EKF_sym.augment, ekf_sym.py:365-391; the schedule's augment[t]): a fixed permutation
       // of the state (one lane per filter) and of the rows / columns of P, read out of the LDS image (the trace above holds the
       // estimate BEFORE the shift, like the reference's Estimate)
-      if (augs != nullptr && augs[t] != 0) {{
-{_img(E, R)}
-        rn::wave_lds_sync();
-        if (c == 0 && live) {{
-          double xo[{D}];
-#pragma unroll
-          for (int i = 0; i < {D}; i++) xo[i] = sl[{lay.OFF_X} + i];
-{nl.join(f"          sl[{lay.OFF_X + i}] = xo[{src_x[i]}];" for i in range(D) if src_x[i] != i)}
-        }}
-{nl.join(shift)}
-        rn::wave_lds_sync();
-      }}"""
+{_window_shift(spec, cond="augs != nullptr && augs[t] != 0")}"""
   # predict(dt = 0) is skipped only for models where it is symbolically the identity (FilterSpec.identity_at_dt0)
   id0_guard = "true" if not spec.identity_at_dt0() else "dt != 0.0"
   nlc = chr(10)
@@ -601,7 +580,7 @@ def run_kernel(spec):
     after_step=aug)
 
 
-def run_pf_kernel(spec, noise=TABLE):
+def run_pf_kernel(spec, noise=TABLE, msckf=False):
   """k_run_pf of the lane-group family: k_run's structure (GL lanes per filter, rows of P in registers, FPW filters per wavefront) with a
   SCHEDULE PER FILTER, kinds (T, n) and dts (T, n).  Every lane of a group fetches its filter's kind and dt (one address per group), a step
   ahead like the observations.  The scalar phases run on lane c == 0 of the groups that step, each on its own kind and dt.  The matrix phases
@@ -619,21 +598,45 @@ def run_pf_kernel(spec, noise=TABLE):
   `update_{kind}_rows_rpf` takes the values only where `mine`.
 
   noise=DIAG: k_run_dpf, a DIAGONAL NOISE PER ENTRY -- gR is (T, n, zmax), the leading Z doubles of row (t, i) the variances of filter i's entry t.
-  k_run_rpf with rows of zmax doubles, Re[zmax]: requested, waited for and predicated in the same places (`update_{kind}_rows_dpf`)."""
+  k_run_rpf with rows of zmax doubles, Re[zmax]: requested, waited for and predicated in the same places (`update_{kind}_rows_dpf`).
+
+  msckf=True (with noise=TABLE): k_run_epf, the same schedule text with what run_epf_kernel's docstring lists."""
+  assert noise is TABLE or not msckf
   E = spec.dim_err
   _, R, _ = layout(spec)
   lay = w2.slot_tables(spec, RunLayout)[0]
   zmax = max(k.zdim for k in spec.kinds)
-  ZZ = noise.row(zmax)      # doubles per row of gR
+  ZZ, EAM = noise.row(zmax), ea_max(spec)      # doubles per row of gR, of gea
   rows, idx = _row_args(R)
   nlc = chr(10)
   known = " ".join(f"case {k.kind}:" for k in spec.kinds)
-  scal_cases = nlc.join(f"          case {k.kind}: scal_obs_{k.kind}_r(sl, sl + {lay.OFF_Y}); break;" for k in spec.kinds)
-  mat = nlc.join(f"""      {{
+  psfx, usfx = ("_epf", "_epf") if msckf else ("_pf", noise.update)      # the names of the predicated predict / update functions
+  scal_cases, mat = [], []
+  for i, k in enumerate(spec.kinds):      # (extra arguments and feature-track kinds: MSCKF models only, emit.has_run_pf)
+    feat = k.He_sym is not None
+    args = f"sl, sl + {lay.OFF_Y}" + (f", gea + ((int64_t)t * n + base + g) * {EAM}" if ea_count(k) else "") + (f", gR + {i * ZZ}" if feat else "")
+    scal_cases.append(f"          case {k.kind}: scal_obs_{k.kind}_r{'<true>' if feat else ''}({args}); break;")
+    mat.append(f"""      {{
         const bool mine = step && kind == {k.kind};
-        if (__any(mine)) update_{k.kind}_rows{noise.update}({rows}, {"Re" if noise.per_entry else f"gR + {i * ZZ}"}, sP, s_G + gg * {zmax * E}, sl, sl, {idx}, mine{_tl_arg(True)});
-      }}""" for i, k in enumerate(spec.kinds))
+        if (__any(mine)) update_{k.kind}_rows{usfx}({rows}, {"Re" if noise.per_entry else f"gR + {i * ZZ}"}, sP, s_G + gg * {zmax * E}, sl, sl, {idx}, mine{_tl_arg(True)});
+      }}""")
   id0_guard = "true" if not spec.identity_at_dt0() else "dt != 0.0"
+  title, kname, args, after_step = noise.title_wide.format(zmax=zmax, ZZ=ZZ), noise.kernel, "", ""
+  aug_first = aug_now = aug_next = ""
+  if msckf:      # the MSCKF flavour's own (run_epf_kernel), beside the names and the scalar cases' arguments above
+    title = (f"// ---- fused multi-step run, a schedule per filter, MSCKF models: k_run_pf (gR one row per kind) with gea (T, n, {EAM}) extra arguments per entry "
+             "and augs (T, n) or NULL, a window shift after the entry, per group (see emit_wide3.run_epf_kernel) -----------")
+    aug_first = "    int aug_n = augs != nullptr ? augs[base + gg] : 0;\n"
+    aug_now = "      const int aug = aug_n;\n"
+    aug_next = "        if (augs != nullptr) aug_n = augs[tn * n + base + gg];\n"
+    kname, args = "k_run_epf", ", const double* __restrict__ gea, const int32_t* __restrict__ augs"
+    after_step = f"""
+      // MSCKF window shift after this step, per group (k_run's block under the group's own predicate; the trace above holds the estimate
+      // BEFORE the shift): every lane meets the fences, only the shifting groups take the new rows and write x
+      {{
+        const bool sh = step && aug != 0;
+{_window_shift(spec, pad="  ", cond="__any(sh)", guard="sh")}
+      }}"""
   r_first, r_next = "", ""
   if noise.per_entry:
     r_first = f"""    // the group's own row of R, a step ahead like its schedule entry; taken by the updates only where the group carries their kind
@@ -649,31 +652,31 @@ def run_pf_kernel(spec, noise=TABLE):
         for (int i = 0; i < {ZZ}; i++) Re[i] = rp_[i];
       }}"""
   return _fused_run(
-    spec, True, title=noise.title_wide.format(zmax=zmax, ZZ=ZZ), kname=noise.kernel,
+    spec, True, title=title, kname=kname, fsfx=psfx, args=args, after_step=after_step,
     pre_loop="""    bool stepped = false;
     // the group's own schedule entry, a step ahead (every lane of a group reads its filter's: one address per group)
     int kind_n = kinds[base + gg];
     double dt_n = dts[base + gg];
-""" + r_first,
+""" + aug_first + r_first,
     sched=f"""      const int kind = live ? kind_n : 0;
       const double dt = dt_n;
-      {{
+{aug_now}      {{
         const int64_t tn = t + 1 < T ? t + 1 : t;
         kind_n = kinds[tn * n + base + gg];
         dt_n = dts[tn * n + base + gg];
-      }}
+{aug_next}      }}
       bool step = false;
       switch (kind) {{ {known} step = true; break; default: break; }}
       const bool pd = step && ({id0_guard});
       stepped = stepped || step;""",
     update=f"""      if (c == 0 && step) {{
         switch (kind) {{
-{scal_cases}
+{nlc.join(scal_cases)}
           default: break;
         }}
       }}
       rn::wave_lds_sync();
-{mat}{r_next}""",
+{nlc.join(mat)}{r_next}""",
     flags_rule=f"""        int fl = kind <= 0 ? 16 : 8;          // idle entry; a kind the model does not have: untouched either way
         if (step) fl = scal_inject_r(sl, sl + {lay.OFF_X}, norm_quats) | (int)sl[{lay.OFF_FL}];""")
 
@@ -691,6 +694,38 @@ def _shift_maps(spec):
   return src_x, se
 
 
+def _window_shift(spec, cond, pad="", guard=""):
+  """The block `if (cond) { ... }` of the MSCKF window shift, for k_run and k_run_epf alike: the image is written from the rows, lane 0 of a group
+  permutes x, and the rows are re-read out of the image through the fixed permutation (_shift_maps); every lane meets both fences.
+  k_run: `cond` is the wave-uniform augs[t], every live group shifts.  k_run_epf: the block sits `pad` deeper, `cond` asks whether any group of
+  the wavefront shifts and `guard` is the group's own predicate: only the shifting groups write x and take the new rows."""
+  D, E = spec.dim_x, spec.dim_err
+  _, R, _ = layout(spec)
+  lay = w2.slot_tables(spec, RunLayout)[0]
+  d2, d4 = spec.dim_main_err, spec.dim_augment_err
+  src_x, se = _shift_maps(spec)
+  nl = chr(10)
+  shift = []
+  for s in range(R):
+    # (guard: a branch on the group's predicate, not a select per entry: with `row = sh ? image : row` hipcc kept the row arrays in scratch memory,
+    # 256 bytes per lane on the 15-state model; the lanes of the other groups are masked off through the same statements)
+    shift.append(f"{pad}        {f'if ({guard}) ' if guard else ''}{{ const int sr = (rc{s} < {E - d4} ? rc{s} : rc{s} - {E - d4}); const int srow = sr < {d2} ? sr : sr + {d4};")
+    shift += [f"{pad}          row{s}[{j}] = sP[srow * {E} + {se(j)}];" for j in range(E)]
+    shift.append(f"{pad}        }}")
+  return f"""{pad}      if ({cond}) {{
+{_img(E, R, pad=pad)}
+{pad}        rn::wave_lds_sync();
+{pad}        if (c == 0 && {guard or "live"}) {{
+{pad}          double xo[{D}];
+#pragma unroll
+{pad}          for (int i = 0; i < {D}; i++) xo[i] = sl[{lay.OFF_X} + i];
+{nl.join(f"{pad}          sl[{lay.OFF_X + i}] = xo[{src_x[i]}];" for i in range(D) if src_x[i] != i)}
+{pad}        }}
+{nl.join(shift)}
+{pad}        rn::wave_lds_sync();
+{pad}      }}"""
+
+
 def run_epf_kernel(spec):
   """k_run_epf, MSCKF models: k_run_pf (one R per kind) with what k_run alone carried so far, per filter.
     * EXTRA ARGUMENTS PER ENTRY: gea is (T, n, EA), EA the largest kind_eadim.  Lane c == 0 of a group that steps a kind with extra arguments
@@ -705,90 +740,7 @@ def run_epf_kernel(spec):
       The block is skipped when no group of the wavefront shifts.  An entry that did not step its filter (idle, unknown kind) does not shift
       it; one whose projection was rank deficient (flag 4) does, as in k_run.  The trace row is the estimate BEFORE the shift.
   (_fused_run holds the kernel's text.)"""
-  D, E = spec.dim_x, spec.dim_err
-  _, R, _ = layout(spec)
-  lay = w2.slot_tables(spec, RunLayout)[0]
-  zmax = max(k.zdim for k in spec.kinds)
-  ZZ, EAM = zmax * zmax, ea_max(spec)
-  rows, idx = _row_args(R)
-  nlc = chr(10)
-  known = " ".join(f"case {k.kind}:" for k in spec.kinds)
-  scal_cases, mat = [], []
-  for i, k in enumerate(spec.kinds):
-    feat = k.He_sym is not None
-    args = f"sl, sl + {lay.OFF_Y}"
-    if ea_count(k):
-      args += f", gea + ((int64_t)t * n + base + g) * {EAM}"
-    if feat:
-      args += f", gR + {i * ZZ}"
-    scal_cases.append(f"          case {k.kind}: scal_obs_{k.kind}_r{'<true>' if feat else ''}({args}); break;")
-    mat.append(f"""      {{
-        const bool mine = step && kind == {k.kind};
-        if (__any(mine)) update_{k.kind}_rows_epf({rows}, gR + {i * ZZ}, sP, s_G + gg * {zmax * E}, sl, sl, {idx}, mine{_tl_arg(True)});
-      }}""")
-  src_x, se = _shift_maps(spec)
-  d2, d4 = spec.dim_main_err, spec.dim_augment_err
-  shift = []
-  for s in range(R):
-    # (a branch on the group's predicate, not a select per entry: with `row = sh ? image : row` hipcc kept the row arrays in scratch memory,
-    # 256 bytes per lane on the 15-state model; the lanes of the other groups are masked off through the same statements)
-    shift.append(f"          if (sh) {{ const int sr = (rc{s} < {E - d4} ? rc{s} : rc{s} - {E - d4}); const int srow = sr < {d2} ? sr : sr + {d4};")
-    shift += [f"            row{s}[{j}] = sP[srow * {E} + {se(j)}];" for j in range(E)]
-    shift.append("          }")
-  aug = f"""
-      // MSCKF window shift after this step, per group (k_run's block under the group's own predicate; the trace above holds the estimate
-      // BEFORE the shift): every lane meets the fences, only the shifting groups take the new rows and write x
-      {{
-        const bool sh = step && aug != 0;
-        if (__any(sh)) {{
-{_img(E, R, pad="  ")}
-          rn::wave_lds_sync();
-          if (c == 0 && sh) {{
-            double xo[{D}];
-#pragma unroll
-            for (int i = 0; i < {D}; i++) xo[i] = sl[{lay.OFF_X} + i];
-{nlc.join(f"            sl[{lay.OFF_X + i}] = xo[{src_x[i]}];" for i in range(D) if src_x[i] != i)}
-          }}
-{nlc.join(shift)}
-          rn::wave_lds_sync();
-        }}
-      }}"""
-  id0_guard = "true" if not spec.identity_at_dt0() else "dt != 0.0"
-  return _fused_run(
-    spec, True, kname="k_run_epf",
-    title=(f"// ---- fused multi-step run, a schedule per filter, MSCKF models: k_run_pf (gR one row per kind) with gea (T, n, {EAM}) extra arguments per entry "
-           "and augs (T, n) or NULL, a window shift after the entry, per group (see emit_wide3.run_epf_kernel) -----------"),
-    args=", const double* __restrict__ gea, const int32_t* __restrict__ augs",
-    pre_loop="""    bool stepped = false;
-    // the group's own schedule entry, a step ahead (every lane of a group reads its filter's: one address per group)
-    int kind_n = kinds[base + gg];
-    double dt_n = dts[base + gg];
-    int aug_n = augs != nullptr ? augs[base + gg] : 0;
-""",
-    sched=f"""      const int kind = live ? kind_n : 0;
-      const double dt = dt_n;
-      const int aug = aug_n;
-      {{
-        const int64_t tn = t + 1 < T ? t + 1 : t;
-        kind_n = kinds[tn * n + base + gg];
-        dt_n = dts[tn * n + base + gg];
-        if (augs != nullptr) aug_n = augs[tn * n + base + gg];
-      }}
-      bool step = false;
-      switch (kind) {{ {known} step = true; break; default: break; }}
-      const bool pd = step && ({id0_guard});
-      stepped = stepped || step;""",
-    update=f"""      if (c == 0 && step) {{
-        switch (kind) {{
-{nlc.join(scal_cases)}
-          default: break;
-        }}
-      }}
-      rn::wave_lds_sync();
-{nlc.join(mat)}""",
-    flags_rule=f"""        int fl = kind <= 0 ? 16 : 8;          // idle entry; a kind the model does not have: untouched either way
-        if (step) fl = scal_inject_r(sl, sl + {lay.OFF_X}, norm_quats) | (int)sl[{lay.OFF_FL}];""",
-    after_step=aug, fsfx="_epf").strip("\n")      # (one title line, no blank line around: tools/emit_digest.py --without k_run_epf takes exactly this text out)
+  return run_pf_kernel(spec, msckf=True).strip("\n")      # (one title line, no blank line around: tools/emit_digest.py --without k_run_epf takes exactly this text out)
 
 
 def launch_run_epf():

@@ -1617,14 +1617,7 @@ class BatchedEKF:
     if packed and (exact or not self.has_tri_trace()):
       raise KalmanError(f"run(packed=True): lib{self.name}.so has no packed-triangle trace kernels ({self.name}_has_tri_trace), or exact=True was asked for")
     pshape = (T, nb, self.dim_tri) if packed else (T, nb, self.dim_err, self.dim_err)
-    if out is not None:
-      tx, tP = out
-      for t_, shp in ((tx, (T, nb, self.dim_x)), (tP, pshape)):
-        assert t_.is_contiguous() and t_.dtype == torch.float64 and tuple(t_.shape) == shp and t_.device == self.device, "out: wrong trace buffer"
-    else:
-      tx = torch.empty((T, nb, self.dim_x), dtype=torch.float64, device=self.device) if trace else None
-      tP = torch.empty(pshape, dtype=torch.float64, device=self.device) if trace else None
-    fl = torch.zeros((T, nb), dtype=torch.uint8, device=self.device) if flags else None
+    tx, tP, fl = self._trace_buffers(T, nb, pshape, trace, flags, out)
     if nb == 0:
       return zs, tx, tP, fl
     # contiguous views of the filters' records; the C ABI moves them with 16-byte transfers, so record `lo` has to start on an
@@ -1646,13 +1639,30 @@ class BatchedEKF:
       self._run_stepwise(xv, Pv, kinds, dts, zs, Rd, nb, fl, tx, tP, ea, None if augment is None else np.asarray(augment).reshape(T),
                          symmetrise=not exact)
     if nb == self.batch:          # a strict subset leaves the orchestrator's clock alone: the other filters have not moved
-      if ag is not None and self.msckf:
-        for t_, a_ in zip(ts, np.asarray(augment).reshape(T)):
-          if a_:
-            self.augment_times = self.augment_times[1:] + [float(t_)]
+      self._shift_augment_times(ts, augment)
       self.filter_time = float(ts[-1])
     self._keepalive = (kd, dd, Rd, ea, ag)      # the launch is asynchronous: keep its inputs alive
     return zs, tx, tP, fl
+
+  def _trace_buffers(self, T, nb, pshape, trace, flags, out):
+    """The trace and flag buffers of a fused run over nb filters -> (tx, tP, fl), None where not asked for: out = (tx, tP) as the caller
+    preallocated them, checked against (T, nb, D) and pshape (the covariance trace: matrices or packed triangles), else fresh ones."""
+    torch = self._torch
+    if out is not None:
+      tx, tP = out
+      for t_, shp in ((tx, (T, nb, self.dim_x)), (tP, pshape)):
+        assert t_.is_contiguous() and t_.dtype == torch.float64 and tuple(t_.shape) == shp and t_.device == self.device, "out: wrong trace buffer"
+    else:
+      tx = torch.empty((T, nb, self.dim_x), dtype=torch.float64, device=self.device) if trace else None
+      tP = torch.empty(pshape, dtype=torch.float64, device=self.device) if trace else None
+    return tx, tP, (torch.zeros((T, nb), dtype=torch.uint8, device=self.device) if flags else None)
+
+  def _shift_augment_times(self, ts, augment):
+    """The shared timeline's window-shift times (get_augment_times) along a schedule's augment (T,), None: no shifts."""
+    if augment is not None and self.msckf:
+      for t_, a_ in zip(ts, np.asarray(augment).reshape(len(ts))):
+        if a_:
+          self.augment_times = self.augment_times[1:] + [float(t_)]
 
   def _has_batch_run(self):
     """False for a library whose fused multi-step kernel did not fit the register file (gen_code fallback `no_run`: its
@@ -1759,20 +1769,8 @@ class BatchedEKF:
     if not self.per_filter:
       raise KalmanError("run_logs replays per-filter timelines: construct the orchestrator with per_filter=True")
     N, zmax = self.batch, max(self.zdims.values())
-    tt = self._dev(ts)
-    if tt.ndim != 2 or tt.shape[1] != N:
-      raise KalmanError(f"run_logs: ts must be (T, N) = (T, {N}), got {tuple(tt.shape)}")
-    T = int(tt.shape[0])
-    if isinstance(kinds, torch.Tensor):
-      kd = kinds.to(device=self.device, dtype=torch.int32)
-      present = [int(k) for k in torch.unique(kd).tolist() if int(k) > 0]
-    else:
-      kh = np.array(kinds, dtype=np.int32)      # (a writable copy: torch does not take read-only arrays)
-      present = [int(k) for k in np.unique(kh) if int(k) > 0]
-      kd = torch.as_tensor(kh).to(self.device)
-    if tuple(kd.shape) != (T, N):
-      raise KalmanError(f"run_logs: kinds must be (T, N) = ({T}, {N}), got {tuple(kd.shape)}")
-    kd = kd.contiguous()
+    tt, kd, kh, T = self._log_schedule(ts, kinds, "run_logs")
+    present = [int(k) for k in (torch.unique(kd).tolist() if kh is None else np.unique(kh)) if int(k) > 0]
     if T == 0:
       return self._dev(zs, (0, N, zmax)), None, None, None
     for k in present:
@@ -1800,14 +1798,7 @@ class BatchedEKF:
     dts, last = self._log_dts(tt, kd, ft0, "run_logs")
     ft_new = torch.where(last[-1] >= 0, tt.gather(0, last[-1:].clamp(min=0))[0], ft0).contiguous()
     zs = self._dev(zs, (T, N, zmax))
-    if out is not None:
-      tx, tP = out
-      for t_, shp in ((tx, (T, N, self.dim_x)), (tP, (T, N, self.dim_err, self.dim_err))):
-        assert t_.is_contiguous() and t_.dtype == torch.float64 and tuple(t_.shape) == shp and t_.device == self.device, "out: wrong trace buffer"
-    else:
-      tx = torch.empty((T, N, self.dim_x), dtype=torch.float64, device=self.device) if trace else None
-      tP = torch.empty((T, N, self.dim_err, self.dim_err), dtype=torch.float64, device=self.device) if trace else None
-    fl = torch.zeros((T, N), dtype=torch.uint8, device=self.device) if flags else None
+    tx, tP, fl = self._trace_buffers(T, N, (T, N, self.dim_err, self.dim_err), trace, flags, out)
     # (DIAG comes only with its kernel and exact false: _run_logs_noise expands the variances otherwise)
     has = {TABLE: self._has_batch_run_pf, ENTRY: self._has_batch_run_pf_r, DIAG: self._has_batch_run_pf_rd}[noise]
     if self.msckf and noise is TABLE and not exact and self._has_batch_run_pf_ea():
@@ -1834,6 +1825,20 @@ class BatchedEKF:
       self.reset_rewind()
     self._keepalive = (kd, dts, Rd)
     return zs, tx, tP, fl
+
+  def _log_schedule(self, ts, kinds, who):
+    """ts and kinds of N logs on the device, KalmanError (in the name of `who`: run_logs, rts_smooth_logs) unless both are (T, N)
+    -> (tt, kd int32, kh: the host array where kinds did not come as a tensor, else None, T)."""
+    torch = self._torch
+    tt, N = self._dev(ts), self.batch
+    if tt.ndim != 2 or tt.shape[1] != N:
+      raise KalmanError(f"{who}: ts must be (T, N) = (T, {N}), got {tuple(tt.shape)}")
+    T = int(tt.shape[0])
+    kh = None if isinstance(kinds, torch.Tensor) else np.array(kinds, dtype=np.int32)      # (a writable copy: torch does not take read-only arrays)
+    kd = kinds.to(device=self.device, dtype=torch.int32) if kh is None else torch.as_tensor(kh).to(self.device)
+    if tuple(kd.shape) != (T, N):
+      raise KalmanError(f"{who}: kinds must be (T, N) = ({T}, {N}), got {tuple(kd.shape)}")
+    return tt, kd.contiguous(), kh, T
 
   def _log_dts(self, tt, kd, ft0, who):
     """Every entry's dt from its filter's previous entry (or the filter's time ft0 in front of the first one; NaN there: dt = 0): a forward
@@ -2037,10 +2042,7 @@ class BatchedEKF:
     self.filter_time = float(ts[-1])
     if self.msckf:
       self.augment_times = aug0            # the window shifts of the schedule happened ONCE, whatever the passes / chunks
-    if augment is not None and self.msckf:
-      for t_, a_ in zip(ts, np.asarray(augment).reshape(T)):
-        if a_:
-          self.augment_times = self.augment_times[1:] + [float(t_)]
+    self._shift_augment_times(ts, augment)
     if on_chunk is None:
       return xs, (self.unpack_tri(Ps) if packed else Ps)
     return None
@@ -2073,14 +2075,7 @@ class BatchedEKF:
     if not self._has_batch_rts_pf():
       raise KalmanError(f"lib{self.name}.so has no smoother with a schedule per filter ({self.name}_has_batch_rts_pf() == 0)")
     N = self.batch
-    tt = self._dev(ts)
-    if tt.ndim != 2 or tt.shape[1] != N:
-      raise KalmanError(f"rts_smooth_logs: ts must be (T, N) = (T, {N}), got {tuple(tt.shape)}")
-    T = int(tt.shape[0])
-    kd = (kinds.to(device=self.device, dtype=torch.int32) if isinstance(kinds, torch.Tensor) else
-          torch.as_tensor(np.array(kinds, dtype=np.int32)).to(self.device))
-    if tuple(kd.shape) != (T, N):
-      raise KalmanError(f"rts_smooth_logs: kinds must be (T, N) = ({T}, {N}), got {tuple(kd.shape)}")
+    tt, kd, _, T = self._log_schedule(ts, kinds, "rts_smooth_logs")
     xf, Pf = self._dev(trace_x), self._dev(trace_P)      # (converted first: a list has no shape to refuse; a device tensor of the right kind is not copied)
     for what, t_, shp in (("trace_x", xf, (T, N, self.dim_x)), ("trace_P", Pf, (T, N, self.dim_err, self.dim_err))):
       if tuple(t_.shape) != shp:
@@ -2099,8 +2094,7 @@ class BatchedEKF:
     if last_predicted is not None:
       xl = self._dev(last_predicted[0], (N, self.dim_x))
       Pl = self._dev(last_predicted[1], (N, self.dim_err, self.dim_err))
-    nq = self.norm_quats | ((self.norm_quats if norm_quats is None else int(bool(norm_quats))) << 1)
-    self._call("batch_rts_pf", self._p(xf), self._p(Pf), self._p(dts), self._p(act), T, self._p(self.Q), N, nq, self._p(xs), self._p(Ps),
+    self._call("batch_rts_pf", self._p(xf), self._p(Pf), self._p(dts), self._p(act), T, self._p(self.Q), N, self._nq(norm_quats), self._p(xs), self._p(Ps),
                self._p(xl), self._p(Pl), self._stream())
     self._keepalive_rts = (xf, Pf, dts, act, xl, Pl)
     return xs, Ps
@@ -2124,6 +2118,16 @@ class BatchedEKF:
     xs, Ps = self.rts_smooth_logs(tx, tP, ts, kinds, t0=t0, norm_quats=norm_quats, inplace=True)
     return xs, Ps, ys, fl
 
+  def _nq(self, norm_quats):
+    """The smoothers' nq argument.  bit 0: the recomputed predicted states are renormalised like the forward pass did (a property of the
+    filter); bit 1: the reference's norm_quats argument (smoothed states; None: as the filter)."""
+    return self.norm_quats | ((self.norm_quats if norm_quats is None else int(bool(norm_quats))) << 1)
+
+  def _batch_rts(self, xf, Pf, td, m, norm_quats, xs, Ps, xl, Pl, packed):
+    """The launch of rts_smooth (the whole batch) and _rts_on (m filters, in place): batch_rts, or batch_rts_tri over packed triangles."""
+    self._call("batch_rts_tri" if packed else "batch_rts", self._p(xf), self._p(Pf), self._p(td), int(xf.shape[0]), self._p(self.Q), m, self._nq(norm_quats),
+               self._p(xs), self._p(Ps), self._p(xl), self._p(Pl), self._stream())
+
   def _rts_on(self, tx, tP, ts, m, norm_quats, packed=False):
     """In-place backward pass over a trace of m filters (m <= batch); packed: tP holds packed lower triangles (batch_rts_tri)."""
     torch = self._torch
@@ -2131,9 +2135,7 @@ class BatchedEKF:
       raise KalmanError(f"lib{self.name}.so has no batch_rts entry point")
     T = int(tx.shape[0])
     td = self._dev(np.asarray(ts, dtype=np.float64) if not isinstance(ts, torch.Tensor) else ts, (T,))
-    nq = self.norm_quats | ((self.norm_quats if norm_quats is None else int(bool(norm_quats))) << 1)
-    self._call("batch_rts_tri" if packed else "batch_rts", self._p(tx), self._p(tP), self._p(td), T, self._p(self.Q), m, nq, self._p(tx), self._p(tP),
-               None, None, self._stream())
+    self._batch_rts(tx, tP, td, m, norm_quats, tx, tP, None, None, packed)
     self._keepalive_rts = (tx, tP, td)
     return tx, tP
 
@@ -2172,10 +2174,6 @@ class BatchedEKF:
       Pl = self._dev(last_predicted[1], (self.batch, self.dim_err, self.dim_err))
       if packed:
         Pl = self.pack_tri(Pl)
-    # bit 0: the recomputed predicted states are renormalised like the forward pass did (a property of the filter);
-    # bit 1: the reference's norm_quats argument (smoothed states)
-    nq = self.norm_quats | ((self.norm_quats if norm_quats is None else int(bool(norm_quats))) << 1)
-    self._call("batch_rts_tri" if packed else "batch_rts", self._p(xf), self._p(Pf), self._p(td), T, self._p(self.Q), self.batch, nq, self._p(xs), self._p(Ps),
-               self._p(xl), self._p(Pl), self._stream())
+    self._batch_rts(xf, Pf, td, self.batch, norm_quats, xs, Ps, xl, Pl, packed)
     self._keepalive_rts = (xf, Pf, td, xl, Pl)
     return xs, Ps

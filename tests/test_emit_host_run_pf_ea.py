@@ -177,3 +177,30 @@ def test_msckf_per_filter_run_on_the_host(tmp_path):
   set_lds_fill(lib, LDS_FILLS[0][1])
   for a, b, label in zip(got["NaN"], got["1e30"], ("x", "P", "y", "flags", "trace x", "trace P")):
     assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), f"{name} {label}: the result depends on what LDS held at workgroup entry"
+
+
+def _window_shift_statements(kernel_text):
+  """The statements of a fused run's MSCKF window shift that move numbers: lane 0's permutation of x, the row index of every row slot and the
+  rows re-read out of the image -- without indentation and without the guard `if (sh)` of the per-group variant."""
+  lines = kernel_text.split("// MSCKF window shift after this step", 1)[1].split("\n    }\n", 1)[0].splitlines()      # up to the end of the step loop
+  lines = [re.sub(r"^if \(sh\) (?=\{ const int sr\b)", "", line.strip()) for line in lines]
+  return [line for line in lines if re.match(r"sl\[\d+\] = xo\[\d+\];$|row\d+\[\d+\] = sP\[srow \* \d+ \+ \d+\];$|\{ const int sr = ", line)]
+
+
+@pytest.mark.parametrize("name", ["feature", "feature36"])
+def test_both_fused_runs_shift_the_window_with_the_same_statements(name):
+  """k_run shifts every filter of the wavefront at once, k_run_epf each group under its own predicate: one builder (emit_wide3._window_shift)
+  prints both blocks, and whatever its parameters change, the permutation of x and the rows taken out of the image are the same statements."""
+  from examples.feature_kf import FeatureKalman, WideFeatureKalman
+  from rednose_amd.codegen import emit_wide3, tuning
+  from rednose_amd.codegen.spec import build_spec
+  spec = build_spec(**{"feature": FeatureKalman, "feature36": WideFeatureKalman}[name].model())
+  with tuning.using_model(spec):
+    shared, per_group = emit_wide3.run_kernel(spec), emit_wide3.run_epf_kernel(spec)
+  assert "void k_run(" in shared and "void k_run_epf(" in per_group
+  a, b = _window_shift_statements(shared), _window_shift_statements(per_group)
+  R, D, E = emit_wide3.layout(spec)[1], spec.dim_x, spec.dim_err
+  assert sum(s.startswith("row") for s in a) == R * E and sum(s.startswith("{ const int sr") for s in a) == R
+  assert 0 < sum(s.startswith("sl[") for s in a) <= D
+  assert a == b
+  assert sum("if (sh) { const int sr" in line for line in per_group.splitlines()) == R and "if (sh)" not in shared
